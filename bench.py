@@ -11,7 +11,12 @@ full model replica and the replicas are averaged by the library's RCCL group
 (include/w2v_dev.h w2v_group_*, overlapped with the next round) after every
 step (weak scaling); torch.distributed (gloo) carries only control messages.
 
-Prints ONE JSON line on rank 0 (metric/value/unit/... + roofline + cpu_baseline).
+Prints ONE JSON line on rank 0 (metric/value/unit/ms_per_step/... + roofline).
+A plain run sets up, warms up, times --steps steps and prints that line;
+--full adds the legs that take runs of their own (cpu_baseline);
+--dump-outputs DIR writes reproducible outputs as .npy: a row sample of the
+matrices after a short one-wavefront probe step from the initial model, the
+device counters and the update policy used (dump_outputs).
 """
 from __future__ import annotations
 
@@ -96,7 +101,14 @@ def parse():
     ap.add_argument("--min-count", type=int, default=5)
     ap.add_argument("--table-size", type=int, default=100_000_000)
     ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline budget (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs the headline figure does not need (the CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write DIR/<name>.npy: a seeded row sample of W / C / S (float32) after "
+                         "a reproducible one-wavefront probe step from the initial model, and the device counters "
+                         "and update policy of the timed steps (float64); the timed steps' own matrices differ "
+                         "from run to run (Hogwild) and are not written")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: CPU baseline budget (0 = skip)")
     # update policy of the parallel schedule (include/w2v_dev.h); defaults = the library's
     ap.add_argument("--hot-rows", type=int, default=-2,
                     help="rows updated with atomics (-2 auto from the corpus statistics, -1 all, 0 none = plain "
@@ -228,14 +240,19 @@ def main():
     tr.upload_vocab(keep, bounds, codes, points, coff)
     pitch = tr.row_pitch()  # the kernels' row width (64 x floats per lane), zero padding
     vrows = V
-    gW = torch.Generator(device=dev)
-    gW.manual_seed(args.seed)  # identical initial replicas on every rank
-    W = torch.zeros(vrows, pitch, dtype=torch.float32, device=dev)
-    W[:V, :d] = (torch.rand(V, d, generator=gW, device=dev) - 0.5) / d
-    Cm = torch.zeros(vrows, pitch, dtype=torch.float32, device=dev) if (neg > 0 or mode["cbow"]) else None
-    if Cm is not None and mode["cbow"] and mode["hs"]:
-        Cm[:V, :d] = (torch.rand(V, d, generator=gW, device=dev) - 0.5) / d
-    S = torch.zeros(max(vrows, 1), pitch, dtype=torch.float32, device=dev) if mode["hs"] else None
+
+    def initial_model():
+        gW = torch.Generator(device=dev)
+        gW.manual_seed(args.seed)  # identical initial replicas on every rank
+        W = torch.zeros(vrows, pitch, dtype=torch.float32, device=dev)
+        W[:V, :d] = (torch.rand(V, d, generator=gW, device=dev) - 0.5) / d
+        Cm = torch.zeros(vrows, pitch, dtype=torch.float32, device=dev) if (neg > 0 or mode["cbow"]) else None
+        if Cm is not None and mode["cbow"] and mode["hs"]:
+            Cm[:V, :d] = (torch.rand(V, d, generator=gW, device=dev) - 0.5) / d
+        S = torch.zeros(max(vrows, 1), pitch, dtype=torch.float32, device=dev) if mode["hs"] else None
+        return W, Cm, S
+
+    W, Cm, S = initial_model()
     if args.own_model and world == 1:
         Wn = W[:, :d].cpu().numpy()
         Cn = Cm[:, :d].cpu().numpy() if Cm is not None else None
@@ -355,8 +372,32 @@ def main():
                             "useful_note": "6 d sum(M T) over unpadded tiles (M unique contexts, T center + "
                                            "negatives), sum(M T) ~= sum M x mean T"}
 
+    policy_used = tr.policy()
+    if args.dump_outputs and rank == 0:
+        # the reproducible probe step of --dump-outputs (dump_outputs): the initial model again, then
+        # the first sentences of the shard through the same handle under a one-wavefront cap
+        W0, C0, S0 = initial_model()
+        torch.cuda.synchronize()
+        if W is None:  # --own-model: the library holds the matrices
+            tr.upload_model(*(m[:, :d].cpu().numpy() if m is not None else None for m in (W0, C0, S0)))
+        else:
+            for dst, src in ((W, W0), (Cm, C0), (S, S0)):
+                if dst is not None:
+                    dst.copy_(src)
+        del W0, C0, S0
+        torch.cuda.synchronize()
+        tr.set_max_waves(1)
+        tr.set_progress(0)
+        st1 = tr.read_stats()  # set_progress moved the word counter
+        tr.train_sentences_async(0, order_dev.data_ptr(), min(n_sent, PROBE_SENTENCES))
+        torch.cuda.synchronize()
+        st2 = tr.read_stats()
+        probe = dict(zip(("W", "C", "S"), tr.download_model() if W is None else (W, Cm, S)))
+        dump_outputs(args.dump_outputs, delta, policy_used, {k: st2[k] - st1[k] for k in st2}, probe, V, d, args.seed)
+        del probe
+
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         cpu = cpu_baseline(args, counts_v, ids_h, soff_h, neg, mode)
         cpu["gpu_over_cpu"] = round(value / max(cpu["value"], 1e-9), 1)
         cpu["gpu_over_cpu_per_thread_rng"] = round(value / max(cpu["per_thread_rng_value"], 1e-9), 1)
@@ -408,7 +449,7 @@ def main():
                 "kept_centers_per_step": int(delta["centers"] / args.steps),
                 "env_knobs": tr.knobs(),
                 "hot_auto": args.hot_auto,
-                "policy_used": tr.policy(),
+                "policy_used": policy_used,
                 "targets_per_step": int(delta["targets"] / args.steps),
             },
             "roofline": roofline,
@@ -421,6 +462,78 @@ def main():
         log(f"[bench] replica exchange: {rmode_used}, group {averager.info()}")
         averager.close()
     tr.close()
+
+
+STAT_KEYS = ("words", "centers", "contexts", "targets", "draws", "sentences", "nonfinite")  # w2v_dev_stats
+POLICY_KEYS = ("hot_rows", "hot_nodes", "private_rows", "context_rows", "flush_centers", "context_flush",
+               "hot_tau_rows", "private_rate", "wave_cap", "deep")  # DeviceTrainer.policy()
+PROBE_SENTENCES = 64  # sentences of the probe step (one wavefront trains ~60 K words/s)
+PROBE_ROWS = 8192     # rows of each matrix the probe's dump keeps (64 MB is the ceiling of a dump)
+DUMP_BYTES = 60 << 20
+
+
+def dump_rows(n_rows, n_mats, d, seed):
+    """The rows --dump-outputs keeps of an n_rows-row matrix, ascending: all of
+    them if there are at most PROBE_ROWS (and n_mats such float32 matrices fit
+    DUMP_BYTES), else the most frequent half (row 0 = the most frequent word:
+    the rows a short probe touches, and the ones the update policy treats
+    apart) and a seeded uniform sample of the rest. Same arguments, same rows."""
+    keep = min(PROBE_ROWS, DUMP_BYTES // (max(1, n_mats) * d * 4))
+    if n_rows <= keep:
+        return np.arange(n_rows, dtype=np.int64)
+    head = keep // 2
+    rest = np.random.default_rng(seed).choice(n_rows - head, size=keep - head, replace=False) + head
+    return np.concatenate([np.arange(head, dtype=np.int64), np.sort(rest).astype(np.int64)])
+
+
+def dump_outputs(out_dir, stats, policy, probe_stats, probe, V, d, seed):
+    """--dump-outputs: outputs of the timed path's kernels that are the same in
+    every run of one build on the same arguments, so that two builds can be
+    compared file by file.
+
+    The matrices the timed steps themselves leave are NOT such an output. The
+    parallel schedule is Hogwild (wavefronts take sentences as they come and
+    race on the rows they share): two runs of one build on
+    identical inputs, 3 timed + 1 warm-up steps of the default workload,
+    measured a relative Frobenius distance of 0.63 on W and 0.22 on C over a
+    26 K-row sample, so a dump of them cannot tell a changed build from a
+    repeated run. What is written instead:
+
+      W.npy, C.npy, S.npy  float32, a fixed seeded row sample (rows.npy,
+          float64 row numbers; dump_rows) of the unpadded matrices after the
+          PROBE STEP, run after the timed steps: the model is set back to its
+          seeded initial values and the first PROBE_SENTENCES sentences of the
+          shard go through the same handle - same kernels, corpus, Philox key,
+          learning-rate schedule and update-policy settings - under a
+          one-wavefront cap (max_waves 1), where the parallel kernel's order
+          of updates is fixed. Every value is a sum of the kernels' own
+          floating-point updates: wrong gradients, lost updates or another
+          precision change these files.
+      probe_stats.npy      float64, the probe step's device counters (STAT_KEYS)
+      stats.npy            float64, the device counters summed over the timed
+          steps (words trained, centers kept by the subsampling, context and
+          target rows updated, negatives drawn, sentences, non-finite scores):
+          fixed by the corpus, the Philox key and the kernels' sampling
+      policy.npy           float64, the update policy the last timed launch
+          chose (POLICY_KEYS)"""
+    import torch
+
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    probe = {k: m for k, m in probe.items() if m is not None}
+    rows = dump_rows(min(V, min(m.shape[0] for m in probe.values())), len(probe), d, seed)
+    for k, m in probe.items():
+        if isinstance(m, torch.Tensor):
+            m = m[torch.from_numpy(rows).to(m.device), :d].cpu().numpy()
+        else:
+            m = m[rows, :d]
+        np.save(out / f"{k}.npy", np.ascontiguousarray(m, dtype=np.float32))
+    np.save(out / "rows.npy", rows.astype(np.float64))
+    np.save(out / "probe_stats.npy", np.array([probe_stats[k] for k in STAT_KEYS], dtype=np.float64))
+    np.save(out / "stats.npy", np.array([stats[k] for k in STAT_KEYS], dtype=np.float64))
+    np.save(out / "policy.npy", np.array([policy[k] for k in POLICY_KEYS], dtype=np.float64))
+    log(f"[bench] outputs: {', '.join(probe)} ({rows.size} rows x {d} after the probe step), probe_stats, stats, "
+        f"policy -> {out}")
 
 
 def pmc_traffic(args):

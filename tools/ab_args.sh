@@ -1,4 +1,4 @@
-# A/B of two bench.py argument sets on one box, alternating (timing only, --cpu-seconds 0):
+# A/B of two bench.py argument sets on one box, alternating (plain runs: timing only, no CPU baseline leg):
 #   bash tools/ab_args.sh <tag> <config> "<args A>" "<args B>" [reps]
 set -o pipefail
 TAG=$1; CFG=$2; A=$3; B=$4; REPS=${5:-3}

@@ -1,5 +1,5 @@
 # Alternating timing runs of several (library / environment / bench args)
-# variants on one box (timing only, --cpu-seconds 0):
+# variants on one box (plain runs: timing only, no CPU baseline leg):
 #   bash tools/ab_multi.sh <tag> <config> <reps> "<name>|<env assignments>|<bench args>" ...
 # e.g. "prod||" "occ6|W2V_DEV_LIB=word2vec_amd/lib/occ6/libw2v_hip.so W2V_DEBUG_WPB=8|"
 set -o pipefail

@@ -7,7 +7,7 @@
 # steps:
 #   smoke                     __graft_entry__.smoke()
 #   tests[:<pytest -k expr>]  the GPU suite (or the selected tests), no -x, every failure reported
-#   bench:<cN>[:<args>]       one bench.py line of a BASELINE preset (extra args space-separated)
+#   bench:<cN>[:<args>]       one bench.py --full line of a BASELINE preset (extra args space-separated)
 #   profile:<cN>              tools/profile.sh (kernel trace + FETCH_SIZE + WRITE_SIZE passes) +
 #                             tools/pmc_summary.py -> profiles/<tag>_<cN>_* and profiles/pmc_traffic.json
 #   pmc:<cN>[:<passes>]       tools/pmc.sh counter passes (default sq1 sq2 tcc atom)
@@ -36,7 +36,7 @@ for step in "$@"; do
       rc=$?; grep -E "FAILED|ERROR|passed|failed" $OUT/${TAG}_tests.log | tail -12
       [ $rc -eq 0 ] || [ $rc -eq 1 ] || stop "$step" $rc ;;
     bench)
-      timeout -k 10 500 python -u bench.py --config $a $b > $OUT/${TAG}_bench_$a.json 2> $OUT/${TAG}_bench_$a.err || stop "$step" $?
+      timeout -k 10 500 python -u bench.py --full --config $a $b > $OUT/${TAG}_bench_$a.json 2> $OUT/${TAG}_bench_$a.err || stop "$step" $?
       cat $OUT/${TAG}_bench_$a.json ;;
     profile)
       bash tools/profile.sh ${TAG}_$a --config $a --steps 3 || stop "$step" $?
