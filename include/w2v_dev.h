@@ -307,6 +307,40 @@ int w2v_dev_wave_cap_used(w2v_dev* h, int64_t* waves);
  * large-vocabulary HS policy's capped launches; environment W2V_DEEP_HS=1
  * forces it for any HS launch without negatives, 0 disables it). */
 int w2v_dev_deep_used(w2v_dev* h, int32_t* deep);
+/* Everything the last launch's policy decided, in one read-back (additive; for
+ * tests and diagnostics: the accessors above report parts of it). The scale of
+ * each atomic hot Huffman node's deltas goes to the caller's buffer hot_sc of
+ * hot_sc_cap floats (NULL: the count only): n_hot_sc returns how many the
+ * launch used (0: none scaled) and min(n_hot_sc, hot_sc_cap) are copied. */
+typedef struct w2v_launch_plan {
+  int32_t shared;          /* 1: the shared-negatives kernel */
+  int32_t deep;            /* 1: the deep-pipeline HS kernel */
+  int64_t grid;            /* workgroups */
+  int32_t threads;         /* per workgroup */
+  int32_t wpb;             /* waves per workgroup */
+  int64_t lds_bytes;       /* dynamic LDS per workgroup */
+  int64_t wave_cap;        /* w2v_dev_wave_cap_used */
+  int32_t hot_wc;          /* W / C rows [0, hot_wc) take atomics (shared negatives: device-coherent) */
+  int32_t hot_s;           /* Huffman nodes [hot_s, V - 1) take atomics */
+  int64_t hot_atomic;      /* shared negatives: rows [0, hot_atomic) take atomic deltas */
+  int64_t hot_nodes;       /* w2v_dev_policy's hot Huffman nodes */
+  int32_t priv_lo;         /* LDS-private output rows [priv_lo, priv_lo + priv_n) */
+  int32_t priv_n;
+  int32_t ctx_n;           /* LDS-private context rows [0, ctx_n) */
+  float priv_avg;          /* concurrency the private rows' summed deltas are scaled to (0: plain sum) */
+  int32_t flush_every;     /* workgroup centers between flushes of the output rows */
+  int32_t ctx_flush_every; /*   ... of the context rows */
+  int32_t nseg;            /* work items per sentence */
+  int32_t seg_len;         /* tokens per item when nseg > 1 */
+  double private_rate;     /* w2v_dev_private_rate_used */
+  double tau_rows;         /* w2v_dev_hot_tau's row threshold */
+  double hs_hot_avg;       /* concurrency the atomic hot nodes' deltas are scaled to (0: not scaled) */
+  int64_t wide_scratch;    /* ints of per-wave id slices a CBOW window > 127 needs (0: none) */
+  int64_t n_hot_sc;        /* atomic hot Huffman nodes with a scale of their own */
+  float priv_sc[128];      /* flush scale of each private output row */
+  float ctx_sc[64];        /*   ... of each private context row */
+} w2v_launch_plan;
+int w2v_dev_launch_plan(w2v_dev* h, w2v_launch_plan* out, float* hot_sc, int64_t hot_sc_cap);
 /* The replica count the update policy assumes (no reference counterpart: the
  * reference trains one model). w2v_group_create sets it to the group's ranks;
  * the one-GPU rehearsal of an N-rank run (each rank a one-rank group, the

@@ -254,7 +254,7 @@ def test_parallel_runs_and_counts(mode, dim):
     assert abs(st["centers"] - exp_kept) < 6 * sd + (0 if mode.startswith("sg") else 0.01 * exp_kept)
     pol = d.policy()
     if mode == "cbow_hs":
-        # automatic HS flush interval (w2v_dev.hip auto_hs_flush): a 120 K-token
+        # automatic HS flush interval (w2v_policy.cpp auto_hs_flush): a 120 K-token
         # launch gives each workgroup far fewer than 128 x 128 centers -> 64 / 32
         assert (pol["flush_centers"], pol["context_flush"]) == (64, 32), pol
         d.set_private_sync(32, 8.0)  # explicit intervals win over the automatic one
@@ -269,7 +269,7 @@ def test_parallel_runs_and_counts(mode, dim):
 
 @pytest.mark.parametrize("mode", ["sg_ns", "cbow_hs", "sg_hs"])
 def test_parallel_segments_match_whole_sentences(mode, monkeypatch):
-    """Sentence segments as work items (w2v_dev.hip kSegLen): one wave taking a
+    """Sentence segments as work items (w2v_policy.hpp kSegLen): one wave taking a
     sentence's segments in turn trains exactly what it trains taking the whole
     sentence (same centers, windows over the whole sentence, same Philox draws,
     same flush points); fixed alpha, since the schedule reads the word counter,
@@ -502,7 +502,7 @@ def test_parallel_huge_window_reference_alpha_full_concurrency():
     / 124 / 130 / 142 at 1 / 2 / 4 / 8 waves, 667 at 16, 1e7-1e16 at 32-64 and
     non-finite from 128 waves up (profiles/r05a_1_*, r05b_2_*, r05d_4_*), so
     a parallel launch caps its waves in flight by the vocabulary's pressure
-    (effective_max_waves, w2v_dev.hip: here 9; every benchmarked shape stays
+    (effective_max_waves, w2v_policy.cpp: here 9; every benchmarked shape stays
     uncapped) and trains this input to the sequential run's magnitude. An
     explicit 512-wave launch fails LOUDLY (W2V_ERR_DIVERGED) when it diverges,
     never with silent non-finite weights: with round 4's 64 private rows it

@@ -182,7 +182,7 @@ def test_quality_shared_negatives_not_below_oracle(corpus):
 # sequentially, paired. Round 4 ran 2 workgroups per CU on this V 98K corpus
 # and cost -1.20 / -1.25 / -1.00 analogy (+2.8 similarity) in three leases;
 # since round 5 the kernel caps its workgroups in flight by vocabulary
-# pressure (kSnPressure, w2v_dev.hip: 1 per CU here). Measured since (3-seed
+# pressure (kSnPressure, w2v_policy.cpp: 1 per CU here). Measured since (3-seed
 # means, analogy / similarity; profiles/r05a_2_*, r05b_3_*, r05b_tests.log,
 # r05k_tests.log): +0.40 / +0.66, +0.36 / +0.04, +0.39 / +0.72, +0.66 / +0.44,
 # +0.39 / +1.60, +0.22 / -0.05. Analogy: north_star's +-1 both ways.
@@ -361,7 +361,7 @@ def test_quality_headline_scale(name):
 # configs[0]'s corpus under an explicit wave cap that keeps 16-wave workgroups
 # but halves their number (4096 waves). Skip-gram NS with the uncapped launch's
 # 112 private rows collapsed to -69 analogy (a cap of 2048: -41), so a capped
-# launch keeps 64 (w2v_dev.hip tail_ok); skip-gram HS collapsed to -44 with its
+# launch keeps 64 (w2v_policy.cpp tail_ok); skip-gram HS collapsed to -44 with its
 # flush interval and scales counted from the capped grid, so they count the
 # uncapped launch's workgroups (g_flush; profiles/r06aj_*, r06ak_*, r06al_*,
 # r06an_*). One golden seed, the uncapped gate's floor (a capped SG-HS launch

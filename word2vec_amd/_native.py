@@ -69,6 +69,20 @@ class DevStats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class LaunchPlan(C.Structure):
+    """Mirror of w2v_launch_plan."""
+
+    _fields_ = [
+        ("shared", C.c_int32), ("deep", C.c_int32), ("grid", C.c_int64), ("threads", C.c_int32), ("wpb", C.c_int32),
+        ("lds_bytes", C.c_int64), ("wave_cap", C.c_int64), ("hot_wc", C.c_int32), ("hot_s", C.c_int32),
+        ("hot_atomic", C.c_int64), ("hot_nodes", C.c_int64), ("priv_lo", C.c_int32), ("priv_n", C.c_int32),
+        ("ctx_n", C.c_int32), ("priv_avg", C.c_float), ("flush_every", C.c_int32), ("ctx_flush_every", C.c_int32),
+        ("nseg", C.c_int32), ("seg_len", C.c_int32), ("private_rate", C.c_double), ("tau_rows", C.c_double),
+        ("hs_hot_avg", C.c_double), ("wide_scratch", C.c_int64), ("n_hot_sc", C.c_int64),
+        ("priv_sc", C.c_float * 128), ("ctx_sc", C.c_float * 64),
+    ]
+
+
 _P = C.c_void_p
 _I32 = C.c_int32
 _I64 = C.c_int64
@@ -120,6 +134,7 @@ SIGNATURES = {
     "w2v_dev_private_rate_used": (C.c_int, [_P, C.POINTER(_F)]),
     "w2v_dev_wave_cap_used": (C.c_int, [_P, C.POINTER(_I64)]),
     "w2v_dev_deep_used": (C.c_int, [_P, C.POINTER(_I32)]),
+    "w2v_dev_launch_plan": (C.c_int, [_P, C.POINTER(LaunchPlan), C.POINTER(C.c_float), _I64]),
     "w2v_dev_set_replica_count": (C.c_int, [_P, _I32]),
     "w2v_dev_model_max_diff": (C.c_int, [_P, _P, C.POINTER(_F)]),
     "w2v_dev_replica_count": (C.c_int, [_P, C.POINTER(_I32)]),

@@ -18,6 +18,7 @@
 #include "w2v_dev_internal.hpp"
 #include "w2v_kernels.hpp"
 #include "w2v_launch.hpp"
+#include "w2v_policy.hpp"
 #include "w2v_shared.hpp"
 
 namespace w2v {
@@ -63,32 +64,7 @@ void dfree(T*& p) {
 
 }  // namespace
 
-// Work-item size of the parallel Philox schedule (tokens of a sentence per
-// item) and the most items a sentence is cut into.
-constexpr int64_t kSegLen = 128;
-constexpr int64_t kMaxSeg = 64;
-
-// Experiment knobs (environment variables, read ONCE at w2v_dev_create and
-// reported by w2v_dev_knobs / bench.py's JSON): a stray variable must not
-// change a training run silently. -1 / 0 = not set.
-struct Knobs {
-  int64_t seg_len = -1;          // W2V_SEG_LEN: tokens per work item (0 = whole sentences)
-  int wpb = 0;                   // W2V_DEBUG_WPB: waves per workgroup
-  int64_t lds_per_wave = 0;      // W2V_DEBUG_LDS_PER_WAVE: LDS budget per wave (bytes)
-  int64_t max_blocks = 0;        // W2V_DEBUG_MAX_BLOCKS: grid cap
-  int sn_occ = 0;                // W2V_SN_OCC: shared-negatives kernel's waves per SIMD
-  int64_t sn_coherent_rows = -1; // W2V_SN_COHERENT_ROWS
-  int64_t sn_atomic_rows = -1;   // W2V_SN_ATOMIC_ROWS
-  int scale_resident = 0;        // W2V_SCALE_RESIDENT=1: flush scales from the chip's resident workgroups, not the launch's grid
-  double priv_tail_avg = -1;     // W2V_PRIV_TAIL_AVG: private_average of the NS output rows past the 64th (0 = plain sum)
-  int sn_per_cu = 0;             // W2V_SN_PER_CU: shared-negatives workgroups per CU (cap)
-  double ctx_avg = -1;           // W2V_CTX_AVG: private_average of the CBOW context rows (0 = plain sum)
-  double priv_hs_tail_avg = -1;  // W2V_PRIV_HS_TAIL_AVG: private_average of the HS nodes past the 64th
-  double hs_hot_avg = -1;        // W2V_HS_HOT_AVG: concurrent updates the atomic hot HS nodes' deltas are scaled to (0 = none)
-  int wide_hs = -1;              // W2V_WIDE_HS: 0 = never the large-vocabulary HS rule, 1 = at any V (experiments)
-  int deep_hs = -1;              // W2V_DEEP_HS: 1 forces the deep-pipeline HS kernel, 0 never (auto: capped HS launches)
-  std::string desc;             // "NAME=value ..." of the variables that were set
-};
+using w2v::Knobs;  // the experiment knobs (w2v_policy.hpp)
 
 static Knobs read_knobs() {
   Knobs k;
@@ -136,13 +112,7 @@ struct w2v_dev {
   int64_t pitch = 0;
   int32_t d4 = 0;
   int nv = 1;                 // floats per lane per row (instantiated width >= ceil(d / 64))
-  int64_t hot_rows = W2V_HOT_AUTO;  // rows updated with atomics: -2 = auto, -1 = all, 0 = none
-  int32_t private_rows = -1;  // hottest output rows privatised in LDS: -1 = auto, 0 = off
-  int32_t flush_centers = 0;  // workgroup centers between flushes of the privatised rows (0 = auto)
-  float private_average = 8.0f;  // concurrency the privatised rows' summed deltas are scaled to (0 = plain sum)
-  int32_t context_rows = -1;  // CBOW: hottest context rows privatised in LDS too: -1 = auto, 0 = off
-  int32_t context_flush = 0;  // workgroup centers between flushes of the context rows (0 = auto)
-  int64_t max_waves = 0;      // cap on concurrently scheduled wavefronts (0 = as many as fit)
+  w2v::PolicySettings set;   // the update policy's setters (w2v_dev_set_hot_rows ... w2v_dev_set_private_rate)
   bool need_C = false, need_S = false;
   float* W = nullptr;
   float* C = nullptr;
@@ -180,36 +150,18 @@ struct w2v_dev {
   int n_cu = 256;
   bool model_ready = false, vocab_ready = false, corpus_ready = false;
   bool model_bound = false;  // W/C/S owned by the caller
-  // Host statistics of the vocab and corpus, for the update policy's
-  // frequency-derived settings (row_stats: flush scales, automatic hot rows):
+  // Host copies of the vocab and corpus uploads, for the update policy's
+  // frequency-derived settings (stats_of: flush scales, automatic hot rows):
   std::vector<float> keep_h;        // sample probabilities
-  std::vector<double> table_frac;   // unigram-table share of each word
   std::vector<int32_t> leaf_node;   // HS: per word, the deepest internal node of its path (-1: none)
   std::vector<int32_t> node_parent; // HS: parent of each internal node, -1 for the root
   std::vector<int64_t> tok_count;   // corpus token count per word
   uint64_t data_version = 0;        // bumped by every upload that changes the statistics
-  // derived (row_stats): per word f = token share, fk = kept-center share;
-  // per internal node the same summed over the words below it
-  uint64_t stats_version = ~0ull;
-  bool stats_ok = false;
-  double kept_tokens = 0.0;         // expected kept centers of one epoch over the corpus (sum count * min(1, keep))
-  std::vector<double> f, fk, node_f, node_fk;
-  double path_len_f = 0.0, path_len_fk = 0.0;  // HS: mean Huffman code length over the tokens / the kept centers
+  uint64_t stats_version = ~0ull;   // the data_version `stats` was derived from
+  w2v::RowStats stats;              // derived (stats_of); its table_frac is set by the table's upload
   int32_t replicas = 1;             // replicas of the exchange group this handle joined (w2v::set_replicas)
-  int64_t last_wave_cap = 0;        // waves-in-flight cap of the last parallel launch (0: none; effective_max_waves)
-  double hot_tau_rows = 0.0;        // automatic hot rows: expected concurrent updates threshold, W / C rows (0 = by vocab, hot_tau_for)
-  double hot_tau_nodes = 1.0;       //   ... and Huffman nodes
-  double private_rate = -1.0;       // > 0: privatise only rows updated >= this many times per center (private_by_rate);
-                                    // 0: no rate limit; < 0 (default): kSmallLaunchRate for a launch smaller than the chip
-  // the policy the last parallel launch used (w2v_dev_policy)
-  int64_t last_hot_rows = 0, last_hot_nodes = 0;
-  double last_tau_rows = 0.0;
-  double last_private_rate = 0.0;
-  int32_t last_priv = 0, last_ctx = 0;
-  int32_t last_flush = 0, last_ctx_flush = 0;
-  double last_hs_hot_avg = 0.0;     // the hot-node average of the last launch (0: none)
-  bool last_deep = false;           // the last launch ran train_epoch_deep_kernel
-  // per atomic hot Huffman node [hot_s, V - 1): the scale of its deltas (hot_node_scales)
+  w2v::LaunchPlan last_plan;        // what the last launch's policy decided (w2v_dev_launch_plan)
+  // the device copy of last_plan.hot_sc and the scales it holds
   std::vector<float> hot_sc_h;
   float* hot_sc_d = nullptr;
   int64_t hot_sc_cap = 0;
@@ -222,54 +174,12 @@ void set_replicas(w2v_dev* h, int32_t n) { h->replicas = n < 1 ? 1 : n; }
 }  // namespace w2v
 
 // Per-word and per-node shares of the corpus (cached until the next upload).
-static void row_stats(w2v_dev* h) {
-  if (h->stats_version == h->data_version) return;
-  h->stats_version = h->data_version;
-  const int64_t V = h->V;
-  h->stats_ok = V > 0 && (int64_t)h->tok_count.size() == V && (int64_t)h->keep_h.size() == V;
-  h->f.assign((size_t)std::max<int64_t>(V, 0), 0.0);
-  h->fk.assign(h->f.size(), 0.0);
-  h->node_f.clear();
-  h->node_fk.clear();
-  if (!h->stats_ok) return;
-  double N = 0.0, K = 0.0;
-  for (int64_t w = 0; w < V; ++w) {
-    N += (double)h->tok_count[(size_t)w];
-    K += (double)h->tok_count[(size_t)w] * std::min(1.0, (double)h->keep_h[(size_t)w]);
+static const w2v::RowStats& stats_of(w2v_dev* h) {
+  if (h->stats_version != h->data_version) {
+    h->stats_version = h->data_version;
+    w2v::row_stats(h->stats, h->V, h->tok_count, h->keep_h, h->leaf_node, h->node_parent);
   }
-  if (!(N > 0.0 && K > 0.0)) {
-    h->stats_ok = false;
-    return;
-  }
-  h->kept_tokens = K;
-  for (int64_t w = 0; w < V; ++w) {
-    h->f[(size_t)w] = (double)h->tok_count[(size_t)w] / N;
-    h->fk[(size_t)w] = (double)h->tok_count[(size_t)w] * std::min(1.0, (double)h->keep_h[(size_t)w]) / K;
-  }
-  if ((int64_t)h->leaf_node.size() == V && (int64_t)h->node_parent.size() == V - 1) {
-    h->node_f.assign((size_t)(V - 1), 0.0);
-    h->node_fk.assign((size_t)(V - 1), 0.0);
-    for (int64_t w = 0; w < V; ++w)
-      if (h->leaf_node[(size_t)w] >= 0) {
-        h->node_f[(size_t)h->leaf_node[(size_t)w]] += h->f[(size_t)w];
-        h->node_fk[(size_t)h->leaf_node[(size_t)w]] += h->fk[(size_t)w];
-      }
-    for (int64_t j = 0; j < V - 1; ++j)  // a node is created after its children: ids ascend towards the root
-      if (h->node_parent[(size_t)j] >= 0) {
-        h->node_f[(size_t)h->node_parent[(size_t)j]] += h->node_f[(size_t)j];
-        h->node_fk[(size_t)h->node_parent[(size_t)j]] += h->node_fk[(size_t)j];
-      }
-    std::vector<int32_t> depth((size_t)(V - 1), 0);  // the root (V - 2) has depth 0
-    for (int64_t j = V - 3; j >= 0; --j)
-      if (h->node_parent[(size_t)j] > j) depth[(size_t)j] = depth[(size_t)h->node_parent[(size_t)j]] + 1;
-    h->path_len_f = h->path_len_fk = 0.0;
-    for (int64_t w = 0; w < V; ++w)
-      if (h->leaf_node[(size_t)w] >= 0) {
-        const double len = 1.0 + depth[(size_t)h->leaf_node[(size_t)w]];
-        h->path_len_f += h->f[(size_t)w] * len;
-        h->path_len_fk += h->fk[(size_t)w] * len;
-      }
-  }
+  return h->stats;
 }
 
 namespace w2v {
@@ -280,29 +190,27 @@ namespace w2v {
 // the W row of the center and of neg draws, and the center's path. Times the
 // kept fraction of the tokens.
 bool row_update_rates(w2v_dev* h, int k, std::vector<double>& out) {
-  row_stats(h);
+  const w2v::RowStats& st = stats_of(h);
   const int64_t V = h->V;
   out.clear();
-  if (!h->stats_ok || h->tok_count.empty()) return false;
+  if (!st.stats_ok || h->tok_count.empty()) return false;
   double N = 0.0;
   for (int64_t c : h->tok_count) N += (double)c;
-  const double q = N > 0.0 ? h->kept_tokens / N : 0.0;
+  const double q = N > 0.0 ? st.kept_tokens / N : 0.0;
   const double win1 = (double)h->cfg.window + 1.0, neg = (double)h->cfg.negative;
   const bool cbow = h->cfg.cbow != 0;
-  auto u = [&](int64_t r) { return r < (int64_t)h->table_frac.size() ? h->table_frac[(size_t)r] : 0.0; };
   if (k == 2) {
-    if ((int64_t)h->node_f.size() != V - 1) return false;
+    if (!st.has_nodes(V)) return false;
     out.resize((size_t)(V - 1));
-    for (int64_t j = 0; j < V - 1; ++j)
-      out[(size_t)j] = q * (cbow ? h->node_fk[(size_t)j] : win1 * h->node_f[(size_t)j]);
+    for (int64_t j = 0; j < V - 1; ++j) out[(size_t)j] = q * st.node_rate(j, cbow, win1);
     return true;
   }
   out.resize((size_t)V);
   for (int64_t r = 0; r < V; ++r) {
-    const double f = h->f[(size_t)r], fk = h->fk[(size_t)r];
+    const double f = st.f[(size_t)r], fk = st.fk[(size_t)r];
     double m;
-    if (k == 0) m = cbow ? (neg > 0 ? fk + neg * u(r) : 0.0) : fk;
-    else m = cbow ? win1 * f : win1 * (f + neg * u(r));
+    if (k == 0) m = cbow ? (neg > 0 ? fk + neg * st.u(r) : 0.0) : fk;
+    else m = cbow ? win1 * f : win1 * (f + neg * st.u(r));
     out[(size_t)r] = q * m;
   }
   return true;
@@ -313,68 +221,23 @@ namespace {
 
 using KernelFn = w2v::KernelFn;
 
-KernelFn kernel_for(const w2v_dev* h) {
-  const bool cb = h->cfg.cbow != 0, hs = h->cfg.hs != 0, ns = h->cfg.negative > 0;
-  const bool rp = h->rng == W2V_RNG_REPLAY;
-  const bool wd = 2 * h->cfg.window + 1 > w2v::kWave;  // CBOW's lane-per-position context set no longer fits
-  switch (h->nv) {
-    case 1: return w2v::pick_train_nv1(cb, hs, ns, rp, wd);
-    case 2: return w2v::pick_train_nv2(cb, hs, ns, rp, wd);
-    case 3: return w2v::pick_train_nv3(cb, hs, ns, rp, wd);
-    case 4: return w2v::pick_train_nv4(cb, hs, ns, rp, wd);
-    case 5: return w2v::pick_train_nv5(cb, hs, ns, rp, wd);
-    case 6: return w2v::pick_train_nv6(cb, hs, ns, rp, wd);
-    case 8: return w2v::pick_train_nv8(cb, hs, ns, rp, wd);
-    case 12: return w2v::pick_train_nv12(cb, hs, ns, rp, wd);
-    case 16: return w2v::pick_train_nv16(cb, hs, ns, rp, wd);
-    case 24: return w2v::pick_train_nv24(cb, hs, ns, rp, wd);
-    default: return w2v::pick_train_nv32(cb, hs, ns, rp, wd);
-  }
-}
-
-KernelFn kernel_deep_for(const w2v_dev* h) {
-  const bool cb = h->cfg.cbow != 0;
-  switch (h->nv) {
-    case 1: return w2v::pick_train_deep_nv1(cb);
-    case 2: return w2v::pick_train_deep_nv2(cb);
-    case 3: return w2v::pick_train_deep_nv3(cb);
-    case 4: return w2v::pick_train_deep_nv4(cb);
-    case 5: return w2v::pick_train_deep_nv5(cb);
-    case 6: return w2v::pick_train_deep_nv6(cb);
-    case 8: return w2v::pick_train_deep_nv8(cb);
-    case 12: return w2v::pick_train_deep_nv12(cb);
-    case 16: return w2v::pick_train_deep_nv16(cb);
-    case 24: return w2v::pick_train_deep_nv24(cb);
-    default: return w2v::pick_train_deep_nv32(cb);
-  }
-}
-
-w2v::ApplyFn apply_for(const w2v_dev* h) {
-  switch (h->nv) {
-    case 1: return w2v::pick_apply_nv1();
-    case 2: return w2v::pick_apply_nv2();
-    case 3: return w2v::pick_apply_nv3();
-    case 4: return w2v::pick_apply_nv4();
-    case 5: return w2v::pick_apply_nv5();
-    case 6: return w2v::pick_apply_nv6();
-    case 8: return w2v::pick_apply_nv8();
-    case 12: return w2v::pick_apply_nv12();
-    case 16: return w2v::pick_apply_nv16();
-    case 24: return w2v::pick_apply_nv24();
-    default: return w2v::pick_apply_nv32();
-  }
-}
-
 // Instantiated row widths (floats per lane): the smallest one covering d
 // (w2v_kernels.hpp kFullVecs relies on it: the vectors below the next smaller
 // width are inside d in every lane).
-int pick_nv(int d) {
-  const int need = (d + w2v::kWave - 1) / w2v::kWave;
-  static const int widths[] = {1, 2, 3, 4, 5, 6, 8, 12, 16, 24, 32};
-  for (int w : widths)
-    if (w >= need) return w;
-  return 32;
+const w2v::NvKernels& kernels_for_need(int need) {
+  for (const w2v::NvKernels& k : w2v::kNvKernels)
+    if (k.nv >= need) return k;
+  return *(std::end(w2v::kNvKernels) - 1);
 }
+int pick_nv(int d) { return kernels_for_need((d + w2v::kWave - 1) / w2v::kWave).nv; }
+
+KernelFn kernel_for(const w2v_dev* h) {
+  const bool wd = 2 * h->cfg.window + 1 > w2v::kWave;  // CBOW's lane-per-position context set no longer fits
+  return kernels_for_need(h->nv).pick_train(h->cfg.cbow != 0, h->cfg.hs != 0, h->cfg.negative > 0,
+                                            h->rng == W2V_RNG_REPLAY, wd);
+}
+KernelFn kernel_deep_for(const w2v_dev* h) { return kernels_for_need(h->nv).pick_train_deep(h->cfg.cbow != 0); }
+w2v::ApplyFn apply_for(const w2v_dev* h) { return kernels_for_need(h->nv).pick_apply(); }
 
 int set_device(w2v_dev* h) {
   HIP_TRY(hipSetDevice(h->device));
@@ -450,6 +313,7 @@ int w2v_dev_create(const w2v_dev_config* cfg, w2v_dev** out) {
   w2v_dev* h = new w2v_dev();
   h->cfg = *cfg;
   h->knobs = read_knobs();
+  h->last_plan.private_rate = h->last_plan.tau_rows = h->last_plan.hs_hot_avg = 0.0;  // no launch yet
   if (cfg->device >= 0) {
     h->device = cfg->device;
   } else {
@@ -601,8 +465,8 @@ int w2v_dev_upload_vocab(w2v_dev* h, int64_t V, const float* keep, const int64_t
   if (dtable) {
     dfree(h->table);
     h->table = dtable;
-    h->table_frac.assign((size_t)V, 0.0);
-    for (size_t r = 0; r < h->table_frac.size(); ++r) h->table_frac[r] = (double)(bounds[r + 1] - bounds[r]) / (double)n;
+    h->stats.table_frac.assign((size_t)V, 0.0);
+    for (size_t r = 0; r < h->stats.table_frac.size(); ++r) h->stats.table_frac[r] = (double)(bounds[r + 1] - bounds[r]) / (double)n;
   }
   if (h->cfg.hs) {
     dfree(h->codes); dfree(h->points); dfree(h->coff);
@@ -631,9 +495,9 @@ int w2v_dev_upload_table(w2v_dev* h, const uint32_t* table, int64_t n) {
   dfree(h->table);
   HIP_TRY(hipMalloc(&h->table, n * sizeof(uint32_t)));
   HIP_TRY(hipMemcpy(h->table, table, n * sizeof(uint32_t), hipMemcpyHostToDevice));
-  h->table_frac.assign((size_t)std::max<int64_t>(h->V, 0), 0.0);
+  h->stats.table_frac.assign((size_t)std::max<int64_t>(h->V, 0), 0.0);
   for (int64_t i = 0; i < n; ++i)
-    if ((int64_t)table[i] < h->V) h->table_frac[table[i]] += 1.0 / (double)n;
+    if ((int64_t)table[i] < h->V) h->stats.table_frac[table[i]] += 1.0 / (double)n;
   ++h->data_version;
   return W2V_OK;
 }
@@ -1045,324 +909,6 @@ int w2v_dev_get_progress(w2v_dev* h, int64_t* cw) {
 
 static int launch_train(w2v_dev* h, int32_t epoch, const int64_t* order_dev, int64_t count);
 
-// Flush scales of the privatised rows (flush_private / sn_flush_private): a
-// row that n of the launch's G workgroups update within one flush interval of
-// k workgroup centers gets its summed delta scaled by 1 / max(1, n / S), S =
-// priv_avg. n is the EXPECTED count, G (1 - exp(-k m)), with m the row's
-// expected updates per center from the corpus and vocab statistics — a fixed
-// function of the row's frequency rank, so the scale does not depend on the
-// schedule (the previous estimator, each workgroup's running fraction of
-// flushes that found the row dirty, was noisy early in a launch). Per kept
-// center, with f(w) = token share, fk(w) = kept-center share, u(w) = unigram
-// table share, and window + 1 the expected number of context positions
-// (Word2Vec.cpp:335-337: b = window - U[0, window-1]):
-//   SG-NS output (C) rows  (window + 1) (f(r) + neg u(r))   positives are contexts (:346-349)
-//   CBOW-NS output (W)     fk(r) + neg u(r)                  positive is the center (:310)
-//   shared negatives (C)   fk(r) + neg u(r)                  center + the window's shared draws
-//   SG-HS nodes            (window + 1) sum_{w below} f(w)   every context's path (:342-345)
-//   CBOW-HS nodes          sum_{w below} fk(w)               the center's path (:304-306)
-//   CBOW context (C) rows  (window + 1) f(r)                 window positions (:288-300)
-// NS output rows 64..127 of the private range (private_rows > 64, or
-// automatically on skip-gram NS with V >= kWidePrivVocab) flush their deltas
-// scaled to at most kPrivTailAverage concurrent contributions instead of the
-// top rows' 8: with 128 private rows (profiles/r05p_*: W2V_PRIV_TAIL_AVG 24 /
-// 40 / 48) configs[0]'s paired gate is -0.02 / -0.61 / -1.60 analogy and the
-// text8-like corpus's -9.1 / -0.21 / +1.28 similarity (the averaged flush
-// damps rows 64..127 less at 40), configs[2]'s +1.40 / -0.16 at 40. Only the
-// large-vocabulary rule (kWidePrivVocab) ships 128 rows by default: at 40 the
-// text8-shaped corpora sit within a point of both gates, too thin a margin.
-// Smaller skip-gram NS vocabularies privatised kSgNsPrivRows = 96 in round 5
-// (r05r: 96 / 112 rows, configs[0] +0.02 / -0.27 analogy, text8-like
-// similarity +0.77..+2.08 / -0.54..+0.52 at 40; configs[0] 316 -> 357 / 374 M
-// words/s). Round 6 (VERDICT r05 "next" 5), with the gates' low ends on the
-// reference band: 128 at 40 scores configs[0] -0.18 and -0.77
-// analogy (the band's low end is -1.05) and the text8-like SG-NS corpus -0.19
-// / +0.08 similarity against the sequential golden (profiles/r06ac_*,
-// r06ad_tests.log) at 387-396 M words/s; 112 scores -0.37 / +0.38 (r06ac_*)
-// at ~374 M; 96 holds configs[0] within 0.05 of the reference in every run of
-// rounds 5-6 at 356 M. Below V 500 K skip-gram NS takes 112: the largest
-// count that keeps configs[0] more than half a point inside its band.
-// Launches smaller than the chip keep the rate limit (private_rate_for).
-constexpr double kPrivTailAverage = 40.0;
-constexpr int64_t kWidePrivVocab = 500000;
-constexpr int64_t kSgNsPrivRows = 112;
-constexpr double kCtxAvgNs = 128.0;      // CBOW-NS context rows (launch_train has the measurements)
-constexpr int64_t kSnPrivRowsWide = 4;  // shared negatives above negative 5 (launch_train)
-// CBOW-HS: 96 private Huffman nodes (64 context rows beside them) on
-// vocabularies >= 50 K. configs[1] (V 71 K, d200: 96 + 63 rows) 426 -> 468 M
-// words/s, its gate +15.9 / +5.9, text8-like CBOW-HS (V 98 K) +19.7..+22.1 /
-// +13.6..+14.3 (profiles/r05al_*). On the planted corpus's small tree the
-// extra nodes cost 6 similarity points at every flush average (8: -6, 4 / 2 /
-// 1: -8 / -14 / -18, 40 / 128: -13 / -18; r05al_4_*, r05am_*, r05an_*), so
-// small vocabularies keep 64; with fewer than 63 context rows beside them
-// (d300: 96 + 31) configs[1] gained 2 % and lost similarity (r05al_1_*, _2_*).
-constexpr int64_t kCbowHsPrivNodes = 96;
-constexpr int64_t kWideHsVocab = 50000;
-// ... and nodes 64..95 flush at up to 4 averaged contributions: at the top
-// nodes' 8 the text8-like CBOW-HS gate had seeds at -5 / -8 / -9 similarity in
-// two suite runs of four (r05ax_tests.log, r05ay_1_*); at 4 / 2 six seed runs
-// each +10.8..+15.0 / +12.95..+13.7, configs[1] +16.6 / +6.5 (r05ay_*).
-constexpr double kCbowHsTailAverage = 4.0;
-// Skip-gram HS: 128 private Huffman nodes (as many as fit: 127 at d300) at up
-// to 4 averaged contributions. With round 4's 64 nodes at 8 it scored 24-27
-// analogy points below the sequential oracle on configs[0]'s corpus (the
-// headline-scale SG-HS gate, new in round 5: every context of every center
-// walks the top of the tree, and nodes 64..127 as hot atomic rows were
-// Hogwild-stale); 64 nodes at 4 / 2 / 1: -21 / -17 / -13.5; 128 at 8: -4 and
-// one seed at -65; 128 at 4 / 2 / 1: +2.2..+3.2 / +7..+9 / +11, each within a
-// point on similarity (profiles/r05as_*, r05at_*, r05au_*, r05av_*).
-// The planted corpus: +4.5 / +1.4 against +3.1 / +0.7 before. Throughput on
-// configs[0]'s corpus 214 -> 309 M words/s, on configs[2]'s 44.0 -> 52.3 M
-// (0.71 -> 0.85 of 8 TB/s).
-constexpr double kSgHsNodeAverage = 4.0;
-
-static void priv_scales(w2v_dev* h, w2v::TrainArgs& a, int64_t G, bool shared) {
-  for (int p = 0; p < w2v::kPrivMax; ++p) a.priv_sc[p] = 1.0f;
-  for (int p = 0; p < w2v::kCtxMax; ++p) a.ctx_sc[p] = 1.0f;
-  if (!(a.priv_avg > 0.0f) || (a.priv_n == 0 && a.ctx_n == 0)) return;
-  row_stats(h);
-  const double S = a.priv_avg, win1 = (double)h->cfg.window + 1.0, neg = (double)h->cfg.negative;
-  const int64_t V = h->V;
-  const bool ok = h->stats_ok;
-  auto sc = [&](double m, int k, double avg) {  // without statistics: every workgroup counted (the most damping)
-    if (!(avg > 0.0)) return 1.0f;
-    const double n = ok ? (double)G * (1.0 - std::exp(-(double)k * m)) : (double)G;
-    return (float)(1.0 / std::max(1.0, n / avg));
-  };
-  auto f = [&](int64_t r) { return ok ? h->f[(size_t)r] : 0.0; };
-  auto fk = [&](int64_t r) { return ok ? h->fk[(size_t)r] : 0.0; };
-  auto u = [&](int64_t r) { return r < (int64_t)h->table_frac.size() ? h->table_frac[(size_t)r] : 0.0; };
-  const bool cbow = h->cfg.cbow != 0;
-  if (a.priv_n > 0) {
-    if (!shared && h->cfg.hs) {
-      const bool nodes = ok && (int64_t)h->node_f.size() == V - 1;
-      for (int p = 0; p < a.priv_n; ++p) {
-        const int64_t j = a.priv_lo + p;
-        const double m = !nodes ? 1.0 : cbow ? h->node_fk[(size_t)j] : win1 * h->node_f[(size_t)j];
-        // skip-gram HS caps the average at kSgHsNodeAverage, CBOW-HS its nodes
-        // past the 64th at kCbowHsTailAverage (W2V_PRIV_HS_TAIL_AVG: experiments)
-        const double Sh = cbow ? S : std::min(S, kSgHsNodeAverage);
-        const double tail = h->knobs.priv_hs_tail_avg >= 0.0 ? h->knobs.priv_hs_tail_avg
-                            : cbow ? std::min(S, kCbowHsTailAverage) : Sh;
-        const double avg = p < 64 ? Sh : tail;
-        a.priv_sc[p] = sc(m, a.flush_every, avg);
-      }
-    } else {
-      for (int p = 0; p < a.priv_n; ++p) {
-        const int64_t r = a.priv_lo + p;
-        const double m = (shared || cbow) ? fk(r) + neg * u(r) : win1 * (f(r) + neg * u(r));
-        const double avg = p < 64 ? S : h->knobs.priv_tail_avg >= 0.0 ? h->knobs.priv_tail_avg : kPrivTailAverage;
-        a.priv_sc[p] = sc(m, a.flush_every, avg);
-      }
-    }
-  }
-  // CBOW context rows: HS averages them like its nodes (S); NS at up to
-  // kCtxAvgNs contributions (launch_train has the measurements).
-  const double Sc = h->knobs.ctx_avg >= 0.0 ? h->knobs.ctx_avg : h->cfg.hs ? S : kCtxAvgNs;
-  for (int p = 0; p < a.ctx_n; ++p) a.ctx_sc[p] = sc(win1 * f(p), a.ctx_flush_every, Sc);
-}
-
-// Privatised rows by update rate (private_rate mu > 0, private_rows = -1): only
-// the output rows (Huffman nodes for HS) and CBOW context rows a center
-// updates at least mu times on average go to LDS. The LDS rows' averaged
-// flush damps every row it holds by up to 8 / workgroups whatever its rate,
-// which a row of moderate rate does not need (atomics keep its updates) and
-// which under-trains it: on a 2 M-token text8-like corpus whose planted role
-// words rank inside the top 64, 64 private rows give SG-NS analogy / similarity
-// 62.7 / 41.2 against the oracle's 69.5 / 65.4; 8 private rows 94.0 / 72.7
-// (profiles/r02q_*). Returns {output rows, context rows}.
-static std::pair<int64_t, int64_t> private_by_rate(w2v_dev* h, double mu) {
-  row_stats(h);
-  const int64_t V = h->V;
-  if (!h->stats_ok) return {64, w2v::kCtxMax};
-  const double win1 = (double)h->cfg.window + 1.0, neg = (double)h->cfg.negative;
-  const bool cbow = h->cfg.cbow != 0;
-  int64_t out = 0, ctx = 0;
-  if (h->cfg.hs) {
-    if ((int64_t)h->node_f.size() == V - 1)
-      for (int64_t j = V - 2; j >= 0 && out < w2v::kPrivMax; --j) {  // nodes nearest the root first
-        const double m = cbow ? h->node_fk[(size_t)j] : win1 * h->node_f[(size_t)j];
-        if (m < mu) break;
-        ++out;
-      }
-  } else {
-    for (int64_t r = 0; r < V && out < w2v::kPrivMax; ++r) {
-      const double u = r < (int64_t)h->table_frac.size() ? h->table_frac[(size_t)r] : 0.0;
-      const double m = cbow ? h->fk[(size_t)r] + neg * u : win1 * (h->f[(size_t)r] + neg * u);
-      if (m < mu) break;
-      ++out;
-    }
-  }
-  for (int64_t r = 0; r < V && ctx < w2v::kCtxMax && cbow; ++r) {
-    if (win1 * h->f[(size_t)r] < mu) break;
-    ++ctx;
-  }
-  return {out, ctx};
-}
-
-// The private-row rate limit a launch of `count` sentences uses (private_rate
-// < 0, the default): kSmallLaunchRate when the launch has fewer sentences than
-// the chip holds waves, else none. Such a launch (a small corpus, a replica's
-// round slice) puts every sentence on its own wave for the whole launch, so
-// every frequent row is held by thousands of waves at once and the LDS rows'
-// averaged flush damps rows that do not need it: text8_small (2 M tokens,
-// 2,000 sentences for 8,192 waves) CBOW-HS at full concurrency scored -9.5 /
-// -18.8 against the sequential oracle with no limit and +24.4 / +18.9 at 0.1;
-// SG-NS +5.3 / -0.2 and +6.1 / +5.2; the planted corpus (3,000 sentences) holds
-// every gate (+10.8 / +4.8, +1.1 / +0.3, +9.7 / +0.3, +19.8 / +2.5 over the four
-// modes; profiles/r03b_small_corpus.log). A launch that fills the chip keeps
-// no limit: there the limit costs 20 % of throughput.
-constexpr double kSmallLaunchRate = 0.1;
-static double private_rate_for(const w2v_dev* h, int64_t count, int64_t max_waves) {
-  if (h->private_rate >= 0.0) return h->private_rate;
-  const int64_t per_simd = h->nv <= 2 ? 8 : 4;  // kMinWaves<NV>
-  int64_t chip = (int64_t)h->n_cu * 4 * per_simd;
-  if (max_waves > 0) chip = std::min(chip, max_waves);
-  return count < chip ? kSmallLaunchRate : 0.0;
-}
-
-// Waves in flight of a parallel per-pair launch (max_waves == 0: as many as
-// fit, unless the vocabulary cannot take them). A kept center updates about
-// T rows (skip-gram: its W row and, per context, neg + 1 NS targets and the
-// context's Huffman path; CBOW: the context rows, neg + 1 targets, the
-// center's path), so `waves` concurrent centers update an average row
-// waves x T / V times at once. Past kPairPressure of that the Hogwild
-// staleness feeds on itself: on the r04a input (window 150, negative 80, V
-// 1,807: T ~ 12 K, every row ~7 times per center) skip-gram's max |W| is 115 /
-// 124 / 130 / 142 at 1 / 2 / 4 / 8 waves, 667 at 16, 1e7-1e16 at 32-64 and
-// non-finite from 128 up, against the sequential reference's 72-119
-// (profiles/r05a_1_*, r05b_2_*, r05d_4_divergence_gpu_probe.log) — and the
-// reference's own OpenMP loop reaches 1.6e5 on 8 threads
-// (profiles/r05_divergence_oracle.log). The cap applies only where it is below
-// the waves the launch would run (the chip's, and at most one per sentence of
-// the launch): at 64 it leaves every benchmarked and gated workload as it was
-// (largest: the planted corpus's SG-HS, 3,000 sentences x 66 nodes / 3.4 K
-// rows = 58; configs[0] 4, configs[1] 1.2, configs[2] 0.4) and holds the
-// r04a input's skip-gram at 9 waves.
-constexpr double kPairPressure = 64.0;
-
-// Hierarchical softmax on a large vocabulary (V >= kWidePrivVocab, round 6):
-// no LDS-private Huffman nodes or context rows, and the waves in flight
-// capped so that the root — every update's first node — has at most
-// kHsRootPressure updates in flight (waves x its expected updates per kept
-// center: skip-gram window + 1, one per context; CBOW 1): plain Hogwild at
-// the reference's own granularity, the atomic hot nodes exact. The round-5
-// policy (127 private nodes flushed as a damped mean) scored 13-19 analogy
-// points BELOW the sequential reference at configs[2]'s scale (SG-HS
-// -18.2 / -0.2, CBOW-HS -5.3..-13.3 / -1.1..-1.2; profiles/r05ba_*, r05be_*,
-// r06a_*, r06b_*), and no damping of the nodes closes it (the hot nodes'
-// deltas scaled to 64 / 16 / 4 / 1 concurrent contributions: -5.4 / +36.5 /
-// +40.8 / +4.4, r06a_2_*). Without private nodes (r06a_2_*, r06b_*, r06c_*):
-// SG-HS -14.9 at all 8 K waves, -5.2 / -4.2 / -0.54 at 2048 / 512 / 256;
-// CBOW-HS -12.5 / -9.9 at 1024 / 256 with private context rows, +1.54 / +0.73
-// at 1536 / 256 without. 256 (skip-gram) and 1536 (CBOW) waves are both
-// 1536 root updates in flight. Text8-sized vocabularies keep the private
-// nodes: there the same rule costs SG-HS 3 analogy points (c1hs, 256 waves:
-// -2.97) and configs[1]'s CBOW-HS its throughput.
-//
-// Between text8's vocabulary and configs[2]'s neither policy is inside the
-// reference's band (round 6, a mid-vocabulary probe golden, `mhs`: SG-HS d200,
-// V 264 K; profiles/r06u_1_*, r06w_1_*, r06x_tests.log): the private-node
-// policy scores +19.2 above the sequential reference (+18.8 above its 16-thread
-// run), the rule -1.0..-1.2 at 256 waves and -0.6..-1.25 at 64-65 (a cap that
-// scales with V, 1.5e-3 root updates in flight per word) against a band whose
-// low edge is the sequential run - 1. Fewer waves do approach the reference at
-// every size measured (V 71 K: -3.2 / -0.6 / -0.2 at 256 / 64 / 32 waves), at
-// a cost of 10-200x the throughput there, so the rule keeps its validated
-// place: V >= kWidePrivVocab, 1536 root updates in flight.
-constexpr double kHsRootPressure = 1536.0;
-static bool wide_hs_rule(const w2v_dev* h) {
-  const bool on = h->knobs.wide_hs == 1 || (h->knobs.wide_hs != 0 && h->V >= kWidePrivVocab);  // knob: 1 forces, 0 never
-  return h->cfg.hs && on && h->sched == W2V_SCHED_PARALLEL && h->update == W2V_UPDATE_PER_PAIR;
-}
-
-static int64_t effective_max_waves(w2v_dev* h, int64_t count) {
-  if (h->max_waves > 0) return h->max_waves;
-  if (h->sched != W2V_SCHED_PARALLEL || h->update != W2V_UPDATE_PER_PAIR) return 0;
-  row_stats(h);
-  if (!h->stats_ok || h->V < 2) return 0;
-  const double win1 = (double)h->cfg.window + 1.0, neg = (double)h->cfg.negative;
-  const double ns = neg > 0.0 ? neg + 1.0 : 0.0;
-  const double T = h->cfg.cbow ? win1 + ns + (h->cfg.hs ? h->path_len_fk : 0.0)
-                               : 1.0 + win1 * (ns + (h->cfg.hs ? h->path_len_f : 0.0));
-  if (!(T > 0.0)) return 0;
-  double cap = std::floor(kPairPressure * (double)h->V / T);
-  if (wide_hs_rule(h) && (int64_t)h->node_f.size() == h->V - 1) {
-    const int64_t root = h->V - 2;
-    const double m = h->cfg.cbow ? h->node_fk[(size_t)root] : win1 * h->node_f[(size_t)root];
-    if (m > 0.0) cap = std::min(cap, std::floor(kHsRootPressure / m));
-  }
-  const int64_t per_simd = h->nv <= 2 ? 8 : 4;  // kMinWaves<NV>
-  const int64_t chip = (int64_t)h->n_cu * 4 * per_simd;
-  // The waves the launch would run: min(chip, count) with count in sentences
-  // is exact also when launch_train cuts sentences into segments (nseg > 1),
-  // because it does so only when the sentences alone fill the grid (count >=
-  // the grid's waves), and then min(chip, count x nseg) = chip = min(chip,
-  // count).
-  return cap < (double)std::min(chip, count) ? std::max<int64_t>(1, (int64_t)cap) : 0;
-}
-
-// Automatic hot rows (hot_rows == W2V_HOT_AUTO): the rows (and Huffman nodes)
-// whose expected number of updates in flight across the chip, waves x their
-// expected updates per center, is at least hot_tau. A row that several
-// wavefronts update at once loses updates under plain read-modify-write and
-// is read stale across the non-coherent XCD L2s, so those rows take
-// memory-side atomics. Measured on the text8-like CBOW-HS workload (DESIGN.md
-// §4.1): a fixed 1000 rows cut through the planted words' Huffman nodes
-// (analogy 19.8 vs the oracle's 21.4); 2000 / 4000 / 16000 rows: 36.7 /
-// 43.3 / 43.0; this rule at threshold 0.5 / 1 / 2: 42.9 / 43.7 / 44.4. At
-// threshold 4 for the W / C rows the planted SG-HS run collapses (analogy
-// 6 vs 89: its center rows, V = 3.4K under 8K waves, fell to plain
-// read-modify-write; profiles/r02c_*). Returns {W / C rows, nodes}.
-// The W / C threshold when hot_tau_rows is 0 (the default) is 1 for every
-// vocabulary. Round 3 used 2 for a large vocabulary (rows' average updates in
-// flight waves x (window + 1) / V <= 0.1: configs[2], 1738 -> 867 atomic rows,
-// +1.1 %); round 4's paired gate at configs[2]'s own scale (d300, V 717K,
-// the sequential oracle's golden, tests/test_gpu_quality.py, 2 seeds) put
-// threshold 2 at -1.0 / -1.2 similarity in two leases and threshold 1 at
-// +0.03 (profiles/r04b_policy_probe_c3.log), for 1.1 % of throughput
-// (96.3 vs 97.4 M words/s, alternating on one box: r04c_ab_tau.log). Higher
-// thresholds lost more (round 3: analogy 99.9 / 99.5 / 93.0 / 94.9 at 1 / 2
-// / 4 / 16, profiles/r03w_*); at 4 the planted SG-HS run (V = 3.4K) collapsed
-// (its center rows fell to plain read-modify-write: analogy 6 vs 89,
-// profiles/r02c_*). The shared-negatives kernel keeps 1 too (its floor of
-// 1000 atomic rows decides there).
-constexpr double kHotTau = 1.0;
-static double hot_tau_for(const w2v_dev* h, double, bool) {
-  return h->hot_tau_rows > 0.0 ? h->hot_tau_rows : kHotTau;
-}
-
-static std::pair<int64_t, int64_t> auto_hot(w2v_dev* h, double waves, bool shared) {
-  row_stats(h);
-  const int64_t V = h->V;
-  if (!h->stats_ok) return {std::min<int64_t>(V, 1000), std::min<int64_t>(std::max<int64_t>(V - 1, 0), 1000)};
-  const double win1 = (double)h->cfg.window + 1.0, tau = hot_tau_for(h, waves, shared);
-  h->last_tau_rows = tau;
-  const bool cbow = h->cfg.cbow != 0, ns = h->cfg.negative > 0;
-  int64_t rows = 0;
-  for (int64_t r = 0; r < V; ++r) {  // largest rate over the row's roles in W and C
-    // Positive-label updates only: an NS output row's negative-sample updates
-    // (label 0, sigma(f) small for most draws) are small. Counting them put
-    // 13K rows (c3) in the atomic class where these give 2.3K, for the same
-    // paired scores and 2.5 % less throughput (profiles/r02b_*, r02c_*).
-    double m;
-    if (shared) m = std::max(win1 * h->fk[(size_t)r], h->fk[(size_t)r]);   // W: window inputs; C: the center
-    else if (cbow) m = std::max(win1 * h->f[(size_t)r], ns ? h->fk[(size_t)r] : 0.0);  // C: contexts; W: center
-    else m = std::max(h->fk[(size_t)r], ns ? win1 * h->f[(size_t)r] : 0.0);            // W: center; C: contexts
-    if (waves * m >= tau) rows = r + 1;
-  }
-  int64_t nodes = 0;
-  if (h->cfg.hs && (int64_t)h->node_f.size() == V - 1)
-    for (int64_t j = 0; j < V - 1; ++j) {
-      const double m = cbow ? h->node_fk[(size_t)j] : win1 * h->node_f[(size_t)j];
-      if (waves * m >= h->hot_tau_nodes) ++nodes;
-    }
-  return {std::min<int64_t>(V, std::max<int64_t>(rows, 64)), nodes};
-}
-
-// Shared-negatives workgroups in flight per (vocab row / row held by a center); launch_train.
-constexpr double kSnPressure = 0.06;
-
 // The shared-negatives minibatch covers skip-gram NS only: a 16 x 16 MFMA tile
 // holds <= 16 unique context rows (2 * window <= 16) and the center + <= 15
 // negatives; its draws are Philox (the reference has no such path to replay).
@@ -1408,76 +954,45 @@ int w2v_dev_train_sentences_async(w2v_dev* h, int32_t epoch, const int64_t* orde
   return launch_train(h, epoch, order_dev, count);
 }
 
-// Flush interval of the HS privatised rows (auto: flush_centers == 0), in
-// centers of a workgroup: the fewest of 64, 128, ..., 1024 that still gives
-// every workgroup at least kHsFlushes flushes per launch (expected kept
-// centers of the launch / its workgroups, from the corpus statistics); the
-// context rows flush at half of it. Staleness is the model change between
-// flushes, i.e. the launch's fraction between them: a long launch can flush
-// less often with the same fraction, a short one (a small corpus, a
-// replica's slice) keeps 64.
-// Round 2 set 128 flushes per workgroup and a 256 cap (configs[1] 152 -> 173
-// M words/s; the planted corpus lost 3-5 similarity points when forced to
-// 256). Round 5, with the private rows' LDS adds no longer the bottleneck
-// (W2V_PRIV_ADD), the flush atomics and the rows' write traffic are: configs[1]
-// at 256 / 128 / 512 / 1024 node-interval (context at half) runs 331-341 /
-// 426 / 443 M words/s (profiles/r05i_1_*, r05j_1_ab_c2_flush.log), its
-// headline-scale paired gate +13.3 / +6.3, +16.4 / +6.3, +13.5 / +2.5
-// (analogy / similarity against the sequential oracle, r05j_2_*): 1024 / 512
-// is the fastest, but not reproducible: the same gate ran +19.3 / +6.0 in the
-// next lease (both seeds moved together, profiles/r05n_tests_*), where 256 /
-// 128 held +13.1..+13.7 / +5.2..+6.5 over five leases and 512 / 256 +16.4 /
-// +6.3 and +17.3 / +6.45 over two. So 32 flushes per workgroup and a 1024
-// cap: configs[1] (25 K kept centers per workgroup) and the text8-like corpus
-// (32 K) take 512 / 256 (text8-like there: +20.0..+26.8 / +13.0..+14.1, as at
-// 128 / 64, r05j_3_*), text8_small (13 K) 256 / 128 (+25.6 / +19.5,
-// r05j_4_*), the planted corpus (2.4 K) keeps 64 / 32.
-constexpr double kHsFlushes = 32.0;
-constexpr int32_t kHsFlushMax = 1024;
-static int32_t auto_hs_flush(w2v_dev* h, int64_t count, int64_t G) {
-  row_stats(h);
-  if (!h->stats_ok || h->n_sent <= 0 || G <= 0) return 64;
-  const double cpw = h->kept_tokens * ((double)count / (double)h->n_sent) / (double)G;
-  int32_t fe = 64;
-  while (fe < kHsFlushMax && 2.0 * fe * kHsFlushes <= cpw) fe *= 2;
-  return fe;
+// What the policy reads of the handle for a launch of `count` sentences.
+static w2v::PolicyInput policy_input(w2v_dev* h, int64_t count, int sn_waves) {
+  w2v::PolicyInput in{h->set, h->knobs, stats_of(h)};
+  in.window = h->cfg.window; in.negative = h->cfg.negative; in.hs = h->cfg.hs != 0; in.cbow = h->cfg.cbow != 0;
+  in.V = h->V; in.pitch = h->pitch; in.nv = h->nv; in.n_cu = h->n_cu;
+  in.sched = h->sched; in.update = h->update; in.rng = h->rng; in.replicas = h->replicas;
+  in.n_sent = h->n_sent; in.max_len = h->max_len; in.count = count; in.sn_waves = sn_waves;
+  return in;
 }
 
-// Atomic hot Huffman nodes (hot_s .. V - 2 below the LDS-private ones): each
-// of their updates is a memory-side add computed from the node as the wave
-// read it, while `waves` x m(node) other updates of the node are in flight
-// (m = its expected updates per kept center: skip-gram (window + 1) x the
-// token share below it, CBOW the kept-center share). With W2V_HS_HOT_AVG = S
-// their deltas are scaled by 1 / max(1, waves m / S): at most S concurrent
-// stale contributions, the damping the private nodes' averaged flush gives
-// the nodes above them.
-static int hot_node_scales(w2v_dev* h, w2v::TrainArgs& a, double waves, int64_t nodes) {
-  const double S = h->knobs.hs_hot_avg >= 0.0 ? h->knobs.hs_hot_avg : 0.0;
-  h->last_hs_hot_avg = 0.0;
-  if (!h->cfg.hs || h->sched != W2V_SCHED_PARALLEL || !(S > 0.0) || nodes <= 0) return W2V_OK;
-  row_stats(h);
-  if (!h->stats_ok || (int64_t)h->node_f.size() != h->V - 1) return W2V_OK;
-  const bool cbow = h->cfg.cbow != 0;
-  const double win1 = (double)h->cfg.window + 1.0;
-  std::vector<float> sc((size_t)nodes);
-  for (int64_t k = 0; k < nodes; ++k) {
-    const int64_t j = a.hot_s + k;
-    const double m = cbow ? h->node_fk[(size_t)j] : win1 * h->node_f[(size_t)j];
-    sc[(size_t)k] = (float)(1.0 / std::max(1.0, waves * m / S));
-  }
-  if (sc != h->hot_sc_h || !h->hot_sc_d) {
-    HIP_TRY(hipStreamSynchronize(h->stream));  // an earlier launch may still read the old scales
-    if (nodes > h->hot_sc_cap) {
-      dfree(h->hot_sc_d);
-      h->hot_sc_cap = 0;
-      HIP_TRY(hipMalloc(&h->hot_sc_d, (size_t)nodes * sizeof(float)));
-      h->hot_sc_cap = nodes;
+// The device buffers a plan asks for: the atomic hot Huffman nodes' scales and
+// the per-wave id slices of a CBOW window past kMaxWideWindow.
+static int launch_buffers(w2v_dev* h, const w2v::LaunchPlan& p, w2v::TrainArgs& a) {
+  if (!p.hot_sc.empty()) {  // the atomic hot Huffman nodes' scales
+    const int64_t nodes = (int64_t)p.hot_sc.size();
+    if (p.hot_sc != h->hot_sc_h || !h->hot_sc_d) {
+      HIP_TRY(hipStreamSynchronize(h->stream));  // an earlier launch may still read the old scales
+      if (nodes > h->hot_sc_cap) {
+        dfree(h->hot_sc_d);
+        h->hot_sc_cap = 0;
+        HIP_TRY(hipMalloc(&h->hot_sc_d, (size_t)nodes * sizeof(float)));
+        h->hot_sc_cap = nodes;
+      }
+      HIP_TRY(hipMemcpy(h->hot_sc_d, p.hot_sc.data(), (size_t)nodes * sizeof(float), hipMemcpyHostToDevice));
+      h->hot_sc_h = p.hot_sc;
     }
-    HIP_TRY(hipMemcpy(h->hot_sc_d, sc.data(), (size_t)nodes * sizeof(float), hipMemcpyHostToDevice));
-    h->hot_sc_h.swap(sc);
+    a.hot_sc = h->hot_sc_d;
   }
-  a.hot_sc = h->hot_sc_d;
-  h->last_hs_hot_avg = S;
+  if (p.wide_scratch > 0) {  // cbow_center_huge: one id slice per wave
+    if (p.wide_scratch > h->wide_scratch_n) {
+      HIP_TRY(hipStreamSynchronize(h->stream));  // an earlier launch may still use the old slices
+      dfree(h->wide_scratch);
+      h->wide_scratch_n = 0;
+      HIP_TRY(hipMalloc(&h->wide_scratch, (size_t)p.wide_scratch * sizeof(int32_t)));
+      h->wide_scratch_n = p.wide_scratch;
+    }
+    a.wide_ids = h->wide_scratch;
+    a.wide_stride = p.wide_stride;
+  }
   return W2V_OK;
 }
 
@@ -1521,370 +1036,40 @@ static int launch_train(w2v_dev* h, int32_t epoch, const int64_t* order_dev, int
   a.key0 = (uint32_t)h->seed; a.key1 = (uint32_t)(h->seed >> 32);
   a.epoch = (uint32_t)epoch;
   a.fixed_alpha = h->fixed_alpha;
-  // Hot rows (memory-side atomic updates) for `waves` updaters in flight:
-  // {W / C rows [0, rows), the `nodes` internal nodes nearest the root}.
-  auto hot_for = [&](double waves, bool shared) -> std::pair<int64_t, int64_t> {
-    const int64_t V = h->V, nV = std::max<int64_t>(V - 1, 0);
-    if (h->hot_rows == W2V_HOT_AUTO) return auto_hot(h, waves, shared);
-    if (h->hot_rows < 0) return {V, nV};
-    return {std::min<int64_t>(h->hot_rows, V), std::min<int64_t>(h->hot_rows, nV)};
-  };
   a.strict = h->sched == W2V_SCHED_SEQUENTIAL ? 1 : 0;
-  // Workgroup shape: up to 16 waves share the LDS-privatised rows (kMaxBlock);
-  // under a wave cap, narrower workgroups so the capped grid still spans the CUs.
-  const int max_wpb = (h->nv <= 6 ? 1024 : 256) / w2v::kWave;
-  int wpb = max_wpb;
-  if (h->knobs.wpb > 0) wpb = std::min(max_wpb, h->knobs.wpb);  // experiments
-  const int64_t max_waves = sn_fn ? h->max_waves : effective_max_waves(h, count);
-  h->last_wave_cap = h->max_waves > 0 ? 0 : max_waves;
-  if (max_waves > 0) {
-    int64_t per = max_waves / (h->n_cu > 0 ? h->n_cu : 1);
-    wpb = 1;
-    while (wpb * 2 <= max_wpb && wpb * 2 <= per) wpb *= 2;
+  HIP_TRY(hipMemsetAsync(h->work, 0, sizeof(unsigned int), h->stream));  // runs while the host plans
+  // the policy (w2v_policy.cpp) decides the rest
+  const KernelFn occ_fn = sn_fn ? sn_fn : kernel_for(h), deep_fn = sn_fn ? sn_fn : kernel_deep_for(h);
+  hipError_t occ_err = hipSuccess;
+  auto occupancy = [&](w2v::OccKernel k, int threads, int64_t lds) {
+    int per_cu = 0;
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
+        &per_cu, k == w2v::kOccTrainDeep ? deep_fn : occ_fn, threads, (size_t)lds);
+    if (e != hipSuccess) occ_err = e;
+    return per_cu;
+  };
+  w2v::LaunchPlan p = w2v::plan_launch(policy_input(h, count, sn_waves), occupancy);
+  if (occ_err != hipSuccess)
+    return fail(W2V_ERR_HIP, std::string("hipOccupancyMaxActiveBlocksPerMultiprocessor: ") + hipGetErrorString(occ_err));
+  // what this launch did not decide keeps the value of the last launch that did (the accessors' contract)
+  if (p.private_rate < 0.0) p.private_rate = h->last_plan.private_rate;
+  if (p.tau_rows < 0.0) p.tau_rows = h->last_plan.tau_rows;
+  if (p.hs_hot_avg < 0.0) p.hs_hot_avg = h->last_plan.hs_hot_avg;
+  a.hot_wc = p.hot_wc; a.hot_s = p.hot_s; a.hot_atomic = p.hot_atomic;
+  a.priv_lo = p.priv_lo; a.priv_n = p.priv_n; a.ctx_n = p.ctx_n; a.priv_avg = p.priv_avg;
+  a.flush_every = p.flush_every; a.ctx_flush_every = p.ctx_flush_every;
+  a.nseg = p.nseg; a.seg_len = p.seg_len;
+  std::memcpy(a.priv_sc, p.priv_sc, sizeof(a.priv_sc));
+  std::memcpy(a.ctx_sc, p.ctx_sc, sizeof(a.ctx_sc));
+  if (!p.shared) {
+    if (p.priv_n > 0) a.priv_M = h->cfg.hs ? h->S : (h->cfg.cbow ? h->W : h->C);
+    if (p.ctx_n > 0) a.ctx_M = h->C;
   }
-  // The low-occupancy deep-pipeline kernel (train_epoch_deep_kernel) for a
-  // capped HS launch (<= 4 waves per workgroup; W2V_DEEP_HS=1 forces it for
-  // any HS launch without negatives, sequential schedules included: parity
-  // tests; 0 never)
-  const bool deep_ok = h->cfg.hs && h->cfg.negative <= 0 && h->rng != W2V_RNG_REPLAY && h->nv <= 12 &&
-                       !(h->cfg.cbow && 2 * h->cfg.window + 1 > w2v::kWave) && !sn_fn;
-  const bool deep = deep_ok && (h->knobs.deep_hs == 1 ||
-                                (h->knobs.deep_hs != 0 && h->sched == W2V_SCHED_PARALLEL && max_waves > 0 &&
-                                 wpb * w2v::kWave <= w2v::kDeepBlock));
-  if (deep) wpb = std::min(wpb, w2v::kDeepBlock / w2v::kWave);
-  h->last_deep = deep;
-  // Flush interval of the privatised rows, in centers of the workgroup (about
-  // 64 centers per wave for NS, 4 per wave for HS whose top nodes every
-  // update touches), and the averaging of their deltas (flush_private). A
-  // flush stalls the flushing wave (its later loads wait for its atomics,
-  // vmcnt is in order) behind every other workgroup's atomics on the same
-  // rows: CBOW-HS runs 105 / 122 / 141 M words/s at 16 / 32 / 64, SG-NS d300
-  // 78 / 90 / 96 M at 64 / 256 / 1024, with the gates passing throughout
-  // (profiles/r01_hs_flush.log, profiles/r01_ns_flush.log).
-  a.flush_every = h->flush_centers > 0 ? h->flush_centers : (h->cfg.hs ? 64 : 1024);
-  a.priv_avg = h->private_average;
-  // LDS privatisation of the output layer's hottest rows (the NS target matrix
-  // — C for skip-gram, W for CBOW — or the top of the Huffman tree for HS)
-  // and, for CBOW, of the hottest context rows of C (contexts are not
-  // subsampled: the most frequent words sit in most windows): as many rows as
-  // fit 10 KiB per wave of the workgroup, <= kPrivMax per range (the dirty masks),
-  // the output rows first. Layout: lds_header_words in w2v_kernels.hpp.
-  size_t lds_bytes = 0;
-  a.priv_M = nullptr;
-  a.priv_lo = 0;
-  a.priv_n = 0;
-  a.ctx_M = nullptr;
-  a.ctx_n = 0;
-  a.ctx_flush_every = h->context_flush > 0 ? h->context_flush : (h->cfg.hs ? 32 : 256);
-  // Large-vocabulary HS (wide_hs_rule) under its wave cap: the top Huffman
-  // nodes in LDS as a write-combining cache, not a damped average — the
-  // workgroup's waves read node + pending delta (each wave's own updates stay
-  // visible to it, as the reference's thread sees its own), and the pending
-  // deltas are added to HBM as a plain SUM after every center of a wave
-  // (flush_every = waves per workgroup). Every node a wave's path visits is
-  // updated once per center in HBM instead of once per context: SG-HS at
-  // configs[2]'s scale -0.66 / +0.11 against the sequential golden at ~2x the
-  // speed (profiles/r06p_1_*; a flush every 8 centers -1.54 / -0.06). The
-  // cap's waves per CU decide the LDS budget (1 workgroup per CU for
-  // skip-gram's 256 waves: 127 nodes at d300). Skip-gram only: CBOW-HS's 1536
-  // waves share a cache four waves to a workgroup, and with it configs[2]'s
-  // corpus scored -0.16..-0.62 against the sequential golden in two runs
-  // (38.5 M words/s, 2x) and DIVERGED in the third (profiles/r06q_*, r06r_*).
-  const bool plain_cache = wide_hs_rule(h) && !h->cfg.cbow && h->private_rows < 0 && max_waves > 0 && !sn_fn;
-  if (h->sched == W2V_SCHED_PARALLEL) {  // the reference-exact schedule keeps per-update rounding
-    const int64_t row_bytes = (int64_t)h->nv * w2v::kWave * (int64_t)sizeof(float);
-    int64_t per_wave = 10 * 1024;
-    if (h->knobs.lds_per_wave > 0) per_wave = h->knobs.lds_per_wave;  // experiments
-    int64_t budget =
-        std::min<int64_t>(160 * 1024, per_wave * (int64_t)wpb) - 4 * w2v::lds_header_words(w2v::kPrivMax, 64);
-    if (plain_cache) {
-      const int64_t n_cu = h->n_cu > 0 ? h->n_cu : 1;
-      const int64_t wg_per_cu = std::max<int64_t>(1, ((max_waves + n_cu - 1) / n_cu + wpb - 1) / wpb);
-      budget = 160 * 1024 / wg_per_cu - 4 * w2v::lds_header_words(w2v::kPrivMax, 64);
-    }
-    int64_t fit = budget / row_bytes;
-    // <= 64 output rows by default for CBOW and HS. Skip-gram NS takes
-    // kSgNsPrivRows (96), on a large vocabulary (>= kWidePrivVocab) up to 128,
-    // rows past the 64th flushed with the gentler kPrivTailAverage
-    // (priv_scales): 128 at the top rows' average cost 12 points of text8-like
-    // similarity (the averaged flush under-trains the less contended rows);
-    // at V >= 500 K rows 64..127 are function words a 50 M-token launch moves
-    // constantly, in a 70-100 K vocabulary rows 96..127 are evaluation words
-    // (text8: "world", "city", "states", "war"). An explicit private_rows may
-    // ask for up to kPrivMax.
-    // CBOW-HS on a vocabulary >= kWideHsVocab takes 96 nodes when the LDS
-    // still holds 64 context rows beside them (kCbowHsPrivNodes).
-    const bool sg_ns = !h->cfg.cbow && !h->cfg.hs;
-    const bool wide_hs = h->cfg.cbow && h->cfg.hs && h->V >= kWideHsVocab && fit >= kCbowHsPrivNodes + w2v::kCtxMax - 1;
-    const bool sg_hs = !h->cfg.cbow && h->cfg.hs;
-    // Skip-gram NS rows past the 64th only on an uncapped launch: they were
-    // measured (and their tail average set) with the chip's whole grid. Under a
-    // wave cap that leaves 16- or 8-wave workgroups but fewer of them, the
-    // top rows' flush scale (priv_scales: per launch workgroup) doubles, and
-    // together with the tail rows configs[0]'s corpus collapsed: 2048 / 4096
-    // waves -41.0 / -68.7 analogy against the sequential golden, 64 rows at the
-    // same caps -0.09 / +0.12, the uncapped launch at 112 rows -0.29
-    // (profiles/r06ai_c1_probe.log, r06aj_*, r06ak_*).
-    const bool tail_ok = max_waves <= 0;
-    const int64_t auto_rows = sg_hs ? w2v::kPrivMax
-                              : !sg_ns ? (wide_hs ? kCbowHsPrivNodes : 64)
-                              : !tail_ok ? 64
-                                       : h->V >= kWidePrivVocab ? w2v::kPrivMax : kSgNsPrivRows;
-    const bool plain_hs = wide_hs_rule(h);  // large-vocabulary HS: no LDS-private nodes / context rows
-    int64_t P = std::min<int64_t>(fit, h->private_rows > 0 || plain_cache ? w2v::kPrivMax : plain_hs ? 0 : auto_rows);
-    if (h->private_rows >= 0) P = std::min<int64_t>(P, h->private_rows);
-    const bool hs = h->cfg.hs != 0;
-    const int64_t avail = hs ? h->V - 1 : h->V;
-    if (P > avail) P = avail;
-    std::pair<int64_t, int64_t> by_rate{P, w2v::kCtxMax};
-    const double rate = private_rate_for(h, count, max_waves);
-    h->last_private_rate = rate;
-    if (rate > 0.0) {
-      by_rate = private_by_rate(h, rate);
-      if (h->private_rows < 0) P = std::min(P, by_rate.first);
-    }
-    if (P > 0) {
-      a.priv_M = hs ? h->S : (h->cfg.cbow ? h->W : h->C);
-      a.priv_lo = (int32_t)(hs ? avail - P : 0);  // HS: the P internal nodes nearest the root (V-2)
-      a.priv_n = (int32_t)P;
-      if (plain_cache) {  // a write-combining cache: summed, flushed after every center of a wave
-        a.priv_avg = 0.0f;
-        if (h->flush_centers <= 0) a.flush_every = wpb;
-      }
-    }
-    // Auto for CBOW. It doubles CBOW-HS throughput and raises its planted-
-    // corpus scores. CBOW-NS (hot rows privatised on both sides of every dot
-    // product) failed the similarity gate at every flush interval while its
-    // context rows were averaged like the output rows (profiles/r01_context_rows.log;
-    // round 5, 8 averaged contributions at 256 / 64 / 32 / 16 centers: planted
-    // similarity -45 / -37 / -20 / -2.6, r05t_2_*). With up to kCtxAvgNs = 128
-    // contributions (priv_scales) at 256 centers it scores as the atomic context
-    // rows do: planted +2.6 / +0.2 (r05u_2_*), configs[1]'s corpus +3.0..+3.5 /
-    // +3.0..+3.6 against +3.2..+3.7 / +3.2..+3.4 (three runs each,
-    // r05w_*_policy_probe.log); 32 / 64 over-train the planted analogy (+41 / +21),
-    // a plain sum is noisy there (per seed -4.4..+5.3 similarity). It runs 4.6x
-    // the atomic context rows on configs[2]'s corpus (50.5 -> 232 M words/s)
-    // and 5.8x on configs[1]'s at d200 / negative 5 (106 -> 613 M; r05v_2_*, r05v_3_*).
-    int64_t Q = h->cfg.cbow ? std::min<int64_t>({fit - P, (int64_t)w2v::kCtxMax, h->V}) : 0;
-    if (h->context_rows >= 0) Q = std::min<int64_t>(Q, h->context_rows);
-    else if (plain_hs) Q = 0;
-    else if (rate > 0.0) Q = std::min(Q, by_rate.second);
-    if (Q > 0) {
-      a.ctx_M = h->C;
-      a.ctx_n = (int32_t)Q;
-    }
-    if (P + Q > 0)
-      lds_bytes = (size_t)(w2v::lds_header_words(P, Q) * (int64_t)sizeof(float) + (P + Q) * row_bytes);
-  }
-  if (sn_fn) {  // shared-negatives minibatch: 2-wave workgroups, static LDS
-    a.priv_M = nullptr;
-    a.ctx_M = nullptr;
-    a.ctx_n = 0;
-    a.item0 = 0;
-    // LDS row slots (kSnPriv in w2v_shared.hpp: 20 KiB of rows, <= 32), parallel
-    // schedule only. The first priv_n hold the workgroup's pending deltas of
-    // the hottest C rows, added to HBM with atomics every flush_centers centers
-    // (auto: up to 10, every 1024 centers); the rest stage the atomic rows'
-    // deltas of each center. Measured on configs[4]: 4 private rows + staged
-    // atomics 72 M words/s vs 61 M with neither, and higher planted /
-    // text8-like scores (profiles/r01_sn_atomic_rows.log); private rows in
-    // every slot run faster still with the same scores: of 8 slots, 8 private
-    // rows +4 % over 4 + 4 staging; of 10 slots (single transpose buffer), 10
-    // private +3.8 % over 4 (profiles/r02z_priv.log, r02z_c5_slots10.log,
-    // r02z_sn_quality_probe*.log). Those measurements are at negative 5. At
-    // configs[4]'s own negative 15 every center draws three times as many of
-    // the hottest C rows, a workgroup's 1024-center pending delta of them is
-    // three times as stale, and the averaged flush costs the text8-like gate 8
-    // similarity points (90.7-91.6 / 62.8-65.1 with 2-32 averaged contributions
-    // against 98.1 / 72.2 with no private rows, the sequential minibatch
-    // scoring 98.3 / 69.7: profiles/r03q_c5_*.log). Round 5 (configs[4]'s
-    // paired gate against the sequential minibatch, 3 seeds per run): 10 rows
-    // fail at every average (1-8: -0.9..-2.1 / -1.7..-5.4; 128 and the plain
-    // sum diverge), 2 / 4 / 6 rows at 4 or 8 pass in every run (4 at 8: +0.16..
-    // +0.45 / +0.27..+1.06 in three; at 4: -0.01..+0.26 / -0.67..+1.30 in five;
-    // the configuration without them +0.04..+0.34 / -0.71..+0.84) and run
-    // 71.7 / 73.2 / 74.0 M words/s against 66.7 M (profiles/r05y_*, r05z_*,
-    // r05aa_*). Above negative 5 the automatic setting keeps 4 private rows
-    // (the other slots stage atomic rows) — for a handle that trains alone:
-    // two replicas summed by the exchange then lose -0.6 / -2.2 analogy on
-    // the 400 M-token replica gate (r05ab_tests.log, r05ad_tests.log; the
-    // rows' divisor assumes one replica's concurrency), so replicas keep none.
-    {
-      const int64_t slots = std::min<int64_t>(32, w2v::kSnPrivBytes / (h->pitch * (int64_t)sizeof(float)));
-      const int64_t wide = h->replicas > 1 ? 0 : kSnPrivRowsWide;
-      const int64_t want = h->private_rows < 0 ? std::min<int64_t>(h->cfg.negative <= 5 ? 10 : wide, slots)
-                                               : h->private_rows;
-      a.priv_n = h->sched == W2V_SCHED_PARALLEL ? (int32_t)std::min<int64_t>({slots, h->V, want}) : 0;
-    }
-    a.flush_every = h->flush_centers > 0 ? h->flush_centers : 1024;
-    const int threads = sn_waves * w2v::kWave;
-    // device-coherent rows (rows_rsrc in w2v_shared.hpp): all for hot_rows =
-    // -1, else at least the rows two XCD L2s' capacity could keep resident
-    const int64_t l2_rows = (int64_t)(8 << 20) / (h->pitch * (int64_t)sizeof(float));
-    int64_t g = 1, g_res = 1;
-    if (h->sched == W2V_SCHED_PARALLEL) {
-      int per_cu = 0;
-      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sn_fn, threads, 0));
-      if (per_cu < 1) per_cu = 1;
-      // Concurrency a vocab can take: every center holds its 2 window + negative
-      // + 1 rows for its whole update, so a small vocab's frequent rows are held
-      // by hundreds of workgroups at once. Workgroups in flight are capped at
-      // kSnPressure x V / (rows per center) (at least one per CU). Measured on
-      // the text8-like gate corpus (V 98K, d512, negative 15, window 5: 26 rows;
-      // the paired gate against the sequential minibatch, 3 seeds, two runs
-      // each, profiles/r05a_2_policy_probe.log): 2 workgroups per CU -1.06 /
-      // +2.57 and -0.78 / +3.00 (analogy / similarity), 1 per CU +0.40 / +0.66
-      // and +0.36 / +0.04. The cap allows 0.06 x 98K / 26 = 226 workgroups there
-      // (-> 1 per CU) and leaves configs[4]'s V 740K at full occupancy (4 per CU:
-      // 1708). Round 1 measured quality holding at 1 per CU for V 3.4K and
-      // collapsing at 4 for V 98K (profiles/r01_sn_residency_experiment.log).
-      if (h->max_waves == 0) {
-        const double rows = 2.0 * h->cfg.window + h->cfg.negative + 1.0;
-        const double cap = kSnPressure * (double)h->V / rows / (double)std::max(1, h->n_cu);
-        per_cu = std::max(1, std::min(per_cu, (int)cap));
-      }
-      if (h->knobs.sn_per_cu > 0) per_cu = std::min(per_cu, h->knobs.sn_per_cu);  // experiments
-      g_res = (int64_t)per_cu * h->n_cu;
-      g = std::min<int64_t>(g_res, count);
-      if (h->max_waves > 0) g = std::max<int64_t>(1, std::min<int64_t>(g, h->max_waves / sn_waves));
-    }
-    // the hot rows (one updater per workgroup) take atomic deltas, as in the
-    // per-pair kernel (parallel schedule only: the sequential one is exact
-    // either way), and at least the rows two XCD L2s could keep resident are
-    // device-coherent
-    // (automatic: at least the fixed 1000 rows of round 1 — a shared-negatives
-    // center holds its ~22 rows for its whole update, longer than a per-pair
-    // update holds one, and the rate rule alone left the text8-like gate 2.4
-    // similarity points below the oracle; profiles/r02s_gpu_tests.log)
-    int64_t hot = hot_for((double)g_res, true).first;
-    if (h->hot_rows == W2V_HOT_AUTO) hot = std::max<int64_t>(hot, std::min<int64_t>(h->V, 1000));
-    a.hot_wc = (int32_t)(h->hot_rows == -1 ? h->V : std::min<int64_t>(h->V, std::max<int64_t>(hot, l2_rows)));
-    if (h->knobs.sn_coherent_rows >= 0) a.hot_wc = (int32_t)std::min<int64_t>(h->V, h->knobs.sn_coherent_rows);  // experiments
-    a.hot_atomic = h->sched == W2V_SCHED_PARALLEL ? hot : 0;
-    if (h->knobs.sn_atomic_rows >= 0) a.hot_atomic = std::min<int64_t>(h->V, h->knobs.sn_atomic_rows);  // experiments
-    priv_scales(h, a, h->knobs.scale_resident ? g_res : g, true);
-    h->last_hot_rows = a.hot_atomic;
-    h->last_hot_nodes = 0;
-    h->last_priv = a.priv_n;
-    h->last_ctx = 0;
-    h->last_flush = a.priv_n > 0 ? a.flush_every : 0;
-    h->last_ctx_flush = 0;
-    HIP_TRY(hipMemsetAsync(h->work, 0, sizeof(unsigned int), h->stream));
-    hipLaunchKernelGGL(sn_fn, dim3((unsigned)g), dim3(threads), 0, h->stream, a);
-    HIP_TRY(hipGetLastError());
-    return W2V_OK;
-  }
-  const KernelFn occ_fn = kernel_for(h);  // the hot-row rule counts the regular kernel's residency
-  KernelFn fn = deep ? kernel_deep_for(h) : occ_fn;
-  HIP_TRY(hipMemsetAsync(h->work, 0, sizeof(unsigned int), h->stream));
-  dim3 grid(1), block(64);
-  int64_t resident_waves = 1, resident_wg = 1, uncapped_wg = 1;
-  if (h->sched == W2V_SCHED_PARALLEL) {
-    const int threads = wpb * w2v::kWave;
-    int per_cu = 0, per_cu_occ = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, lds_bytes));
-    // (the write-combining node cache of a capped HS launch does not change
-    // which nodes the chip's waves contend on: its hot set is counted as
-    // without the cache, the set its quality was measured with)
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_occ, occ_fn, threads, plain_cache ? 0 : lds_bytes));
-    if (per_cu < 1) per_cu = 1;
-    if (per_cu_occ < 1) per_cu_occ = 1;
-    const int64_t resident = (int64_t)per_cu * h->n_cu;
-    resident_waves = (int64_t)per_cu_occ * h->n_cu * (max_wpb);
-    resident_wg = resident;
-    // the workgroups of max_wpb waves the launch would run without its cap
-    uncapped_wg = std::min<int64_t>((count + max_wpb - 1) / max_wpb, (int64_t)per_cu_occ * wpb * h->n_cu / max_wpb);
-    const int64_t need = (count + wpb - 1) / wpb;
-    int64_t g = need < resident ? need : resident;
-    if (max_waves > 0 && (max_waves + wpb - 1) / wpb < g) g = (max_waves + wpb - 1) / wpb;
-    if (h->knobs.max_blocks > 0 && h->knobs.max_blocks < g) g = h->knobs.max_blocks;  // diagnostics only
-    grid = dim3((unsigned)g);
-    block = dim3(threads);
-  }
-  a.hot_sc = nullptr;
-  {
-    // The rule counts every wave the chip could run, not this launch's grid:
-    // a small launch (a round's slice, a wave cap) still spreads over the XCDs,
-    // whose L2s keep stale copies of the rows they read however few waves run
-    // (measured: two replicas on one GPU trained in 1/8-epoch slices collapsed
-    // to analogy 3 with the launch-grid count; tests/test_gpu_replicas.py).
-    const std::pair<int64_t, int64_t> hot = hot_for((double)resident_waves, false);
-    a.hot_wc = (int32_t)hot.first;
-    a.hot_s = (int32_t)((h->V - 1) - hot.second);  // the `nodes` internal nodes nearest the root (the root is V-2)
-    h->last_hot_rows = hot.first;
-    h->last_hot_nodes = h->cfg.hs ? hot.second : 0;
-    h->last_priv = a.priv_n;
-    h->last_ctx = a.ctx_n;
-    if (int rc = hot_node_scales(h, a, (double)resident_waves, hot.second)) return rc;
-  }
-  // Sentence segments as work items (parallel Philox schedule): the launch's
-  // last round shrinks from a whole sentence per wave to one segment. With
-  // ~1000-token sentences and a few thousand resident waves, whole sentences
-  // leave most of the chip idle for the last ~1/rounds of the launch. Only
-  // when the sentences alone fill the grid: segments must not raise the
-  // number of waves training at once (a small corpus would train its
-  // frequent rows from more waves at once than whole sentences do; the
-  // planted CBOW-HS gate loses 3.6 points of similarity that way).
-  a.nseg = 1;
-  a.seg_len = 0;
-  if (h->sched == W2V_SCHED_PARALLEL && h->rng == W2V_RNG_PHILOX && count >= (int64_t)grid.x * block.x / w2v::kWave) {
-    int64_t seg = kSegLen;
-    if (h->knobs.seg_len >= 0) seg = h->knobs.seg_len;  // experiments; 0 = whole sentences
-    if (seg > 0) {
-      seg = (seg + w2v::kWave - 1) / w2v::kWave * w2v::kWave;
-      int64_t nseg = (h->max_len + seg - 1) / seg;
-      if (nseg > kMaxSeg) {  // very long sentences: longer segments, not more
-        nseg = kMaxSeg;
-        seg = ((h->max_len + nseg - 1) / nseg + w2v::kWave - 1) / w2v::kWave * w2v::kWave;
-      }
-      // the dequeue head is 32-bit: items plus one extra dequeue per wave
-      while (nseg > 1 && count * nseg > (int64_t)UINT32_MAX - (1 << 24)) --nseg;
-      if (nseg > 1) {
-        seg = ((h->max_len + nseg - 1) / nseg + w2v::kWave - 1) / w2v::kWave * w2v::kWave;
-        a.nseg = (int32_t)nseg;
-        a.seg_len = (int32_t)seg;
-      }
-    }
-  }
-  // Flush scales from the launch's own grid (the workgroups that actually
-  // race). Counting the chip's resident workgroups instead (W2V_SCALE_RESIDENT)
-  // helps small launches (CBOW-HS in 16 slices per epoch, text8-like: analogy
-  // 24.5 vs 12.2) but over-damps a corpus with fewer sentences than the chip
-  // holds waves (planted CBOW-HS: similarity -13 vs the oracle; profiles/r02l_*, r02r_*).
-  // A wave cap that keeps the uncapped launch's workgroup shape runs fewer of
-  // its workgroups; the flush interval and scales then count the uncapped
-  // launch's workgroups, the ones they were measured with. Counted from the
-  // capped grid, c1hs (SG-HS, configs[0]'s corpus) at 4096 waves collapsed to
-  // -43.9 analogy against the sequential golden (the uncapped launch +2.8),
-  // counted this way +17.7 (profiles/r06al_c1hs_probe.log, r06an_*). Narrower
-  // workgroups keep their own grid: at 2048 waves (8-wave workgroups) the
-  // uncapped count moved configs[1]'s corpus from -1.7 to -4.2, and one wave's
-  // flush must stay its own exact sum.
-  int64_t g_flush = (int64_t)grid.x;
-  if (max_waves > 0 && wpb == max_wpb && h->sched == W2V_SCHED_PARALLEL) g_flush = std::max(g_flush, uncapped_wg);
-  if (h->sched == W2V_SCHED_PARALLEL && h->cfg.hs && a.priv_n + a.ctx_n > 0 && !plain_cache) {
-    const int32_t fe = auto_hs_flush(h, count, g_flush);
-    if (h->flush_centers <= 0) a.flush_every = fe;
-    if (h->context_flush <= 0) a.ctx_flush_every = std::max<int32_t>(1, fe / 2);
-  }
-  h->last_flush = a.priv_n > 0 ? a.flush_every : 0;
-  h->last_ctx_flush = a.ctx_n > 0 ? a.ctx_flush_every : 0;
-  priv_scales(h, a, h->knobs.scale_resident ? resident_wg : g_flush, false);
-  a.wide_ids = nullptr;
-  a.wide_stride = 0;
-  if (h->cfg.cbow && h->cfg.window > w2v::kMaxWideWindow) {  // cbow_center_huge: one id slice per wave
-    const int64_t stride = w2v::huge_stride(h->cfg.window);
-    const int64_t need = (int64_t)grid.x * (int64_t)(block.x / w2v::kWave) * stride;
-    if (need > h->wide_scratch_n) {
-      HIP_TRY(hipStreamSynchronize(h->stream));  // an earlier launch may still use the old slices
-      dfree(h->wide_scratch);
-      h->wide_scratch_n = 0;
-      HIP_TRY(hipMalloc(&h->wide_scratch, (size_t)need * sizeof(int32_t)));
-      h->wide_scratch_n = need;
-    }
-    a.wide_ids = h->wide_scratch;
-    a.wide_stride = stride;
-  }
+  if (int rc = launch_buffers(h, p, a)) return rc;
+  const KernelFn fn = p.deep ? deep_fn : occ_fn;
+  const dim3 grid((unsigned)p.grid), block((unsigned)p.threads);
+  const size_t lds_bytes = (size_t)p.lds_bytes;
+  h->last_plan = std::move(p);
   hipLaunchKernelGGL(fn, grid, block, lds_bytes, h->stream, a);
   HIP_TRY(hipGetLastError());
   return W2V_OK;
@@ -1964,14 +1149,14 @@ int w2v_dev_reset_stats(w2v_dev* h) {
 int w2v_dev_set_max_waves(w2v_dev* h, int64_t n) {
   if (!h) return fail(W2V_ERR_ARG, "null handle");
   if (n < 0) return fail(W2V_ERR_ARG, "max_waves must be >= 0");
-  h->max_waves = n;
+  h->set.max_waves = n;
   return W2V_OK;
 }
 
 int w2v_dev_set_private_rows(w2v_dev* h, int32_t n) {
   if (!h) return fail(W2V_ERR_ARG, "null handle");
   if (n < -1) return fail(W2V_ERR_ARG, "private_rows must be >= -1");
-  h->private_rows = n;
+  h->set.private_rows = n;
   return W2V_OK;
 }
 
@@ -1979,8 +1164,8 @@ int w2v_dev_set_context_private(w2v_dev* h, int32_t rows, int32_t flush_centers)
   if (!h) return fail(W2V_ERR_ARG, "null handle");
   if (rows < -1) return fail(W2V_ERR_ARG, "context rows must be >= -1");
   if (flush_centers < 0) return fail(W2V_ERR_ARG, "flush_centers must be >= 0");
-  h->context_rows = rows;
-  h->context_flush = flush_centers;
+  h->set.context_rows = rows;
+  h->set.context_flush = flush_centers;
   return W2V_OK;
 }
 
@@ -1988,8 +1173,8 @@ int w2v_dev_set_private_sync(w2v_dev* h, int32_t flush_centers, float average_ov
   if (!h) return fail(W2V_ERR_ARG, "null handle");
   if (flush_centers < 0) return fail(W2V_ERR_ARG, "flush_centers must be >= 0");
   if (!(average_over >= 0.0f)) return fail(W2V_ERR_ARG, "average_over must be >= 0");
-  h->flush_centers = flush_centers;
-  h->private_average = average_over;
+  h->set.flush_centers = flush_centers;
+  h->set.private_average = average_over;
   return W2V_OK;
 }
 
@@ -2005,14 +1190,14 @@ int w2v_dev_set_update(w2v_dev* h, int32_t mode) {
 int w2v_dev_set_hot_rows(w2v_dev* h, int64_t hot_rows) {
   if (!h) return fail(W2V_ERR_ARG, "null handle");
   if (hot_rows < W2V_HOT_AUTO) return fail(W2V_ERR_ARG, "hot_rows must be >= -2 (W2V_HOT_AUTO)");
-  h->hot_rows = hot_rows;
+  h->set.hot_rows = hot_rows;
   return W2V_OK;
 }
 
 int w2v_dev_set_private_rate(w2v_dev* h, float mu) {
   if (!h) return fail(W2V_ERR_ARG, "null handle");
   if (!(mu >= 0.0f) && mu != -1.0f) return fail(W2V_ERR_ARG, "private_rate must be >= 0 (or -1: automatic)");
-  h->private_rate = mu;
+  h->set.private_rate = mu;
   return W2V_OK;
 }
 
@@ -2020,42 +1205,50 @@ int w2v_dev_set_hot_auto(w2v_dev* h, float tau_rows, float tau_nodes) {
   if (!h) return fail(W2V_ERR_ARG, "null handle");
   if (!(tau_rows >= 0.0f) || !(tau_nodes > 0.0f))
     return fail(W2V_ERR_ARG, "the automatic hot-row thresholds must be >= 0 (rows; 0 = by vocab) and > 0 (nodes)");
-  h->hot_tau_rows = tau_rows;
-  h->hot_tau_nodes = tau_nodes;
+  h->set.hot_tau_rows = tau_rows;
+  h->set.hot_tau_nodes = tau_nodes;
   return W2V_OK;
 }
 
 int w2v_dev_policy(w2v_dev* h, int64_t* hot_rows, int64_t* hot_nodes, int32_t* private_rows, int32_t* context_rows) {
   if (!h) return fail(W2V_ERR_ARG, "null handle");
-  if (hot_rows) *hot_rows = h->last_hot_rows;
-  if (hot_nodes) *hot_nodes = h->last_hot_nodes;
-  if (private_rows) *private_rows = h->last_priv;
-  if (context_rows) *context_rows = h->last_ctx;
+  if (hot_rows) *hot_rows = h->last_plan.hot_rows;
+  if (hot_nodes) *hot_nodes = h->last_plan.hot_nodes;
+  if (private_rows) *private_rows = h->last_plan.priv_n;
+  if (context_rows) *context_rows = h->last_plan.ctx_n;
   return W2V_OK;
 }
 
 int w2v_dev_hot_tau(w2v_dev* h, float* tau_rows, float* tau_nodes) {
   if (!h) return fail(W2V_ERR_ARG, "null handle");
-  if (tau_rows) *tau_rows = (float)h->last_tau_rows;
-  if (tau_nodes) *tau_nodes = (float)h->hot_tau_nodes;
+  if (tau_rows) *tau_rows = (float)h->last_plan.tau_rows;
+  if (tau_nodes) *tau_nodes = (float)h->set.hot_tau_nodes;
   return W2V_OK;
 }
 
 int w2v_dev_private_rate_used(w2v_dev* h, float* mu) {
   if (!h) return fail(W2V_ERR_ARG, "null handle");
-  if (mu) *mu = (float)h->last_private_rate;
+  if (mu) *mu = (float)h->last_plan.private_rate;
   return W2V_OK;
 }
 
 int w2v_dev_wave_cap_used(w2v_dev* h, int64_t* waves) {
   if (!h) return fail(W2V_ERR_ARG, "null handle");
-  if (waves) *waves = h->last_wave_cap;
+  if (waves) *waves = h->last_plan.wave_cap;
   return W2V_OK;
 }
 
 int w2v_dev_deep_used(w2v_dev* h, int32_t* deep) {
   if (!h || !deep) return fail(W2V_ERR_ARG, "null argument");
-  *deep = h->last_deep ? 1 : 0;
+  *deep = h->last_plan.deep ? 1 : 0;
+  return W2V_OK;
+}
+
+int w2v_dev_launch_plan(w2v_dev* h, w2v_launch_plan* out, float* hot_sc, int64_t hot_sc_cap) {
+  if (!h || !out) return fail(W2V_ERR_ARG, "null argument");
+  *out = h->last_plan;  // the plan's public part
+  out->n_hot_sc = (int64_t)h->last_plan.hot_sc.size();
+  if (hot_sc) std::copy_n(h->last_plan.hot_sc.begin(), std::min(hot_sc_cap, out->n_hot_sc), hot_sc);
   return W2V_OK;
 }
 
@@ -2084,8 +1277,8 @@ int w2v_dev_row_update_rates(w2v_dev* h, int32_t which, double* out, int64_t n) 
 
 int w2v_dev_flush_policy(w2v_dev* h, int32_t* flush_centers, int32_t* context_flush) {
   if (!h) return fail(W2V_ERR_ARG, "null handle");
-  if (flush_centers) *flush_centers = h->last_flush;
-  if (context_flush) *context_flush = h->last_ctx_flush;
+  if (flush_centers) *flush_centers = h->last_plan.priv_n > 0 ? h->last_plan.flush_every : 0;
+  if (context_flush) *context_flush = h->last_plan.ctx_n > 0 ? h->last_plan.ctx_flush_every : 0;
   return W2V_OK;
 }
 

@@ -43,9 +43,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "w2v_limits.hpp"
+
 namespace w2v {
 
-constexpr int kWave = 64;
 // Timing-only experiment builds (tools/r02/exp_variant.sh; never the product):
 // bit 1 skips the hot-row atomics of the targets, bit 2 the global atomics of
 // the private-row flushes, bit 4 the hot context-row atomics of CBOW; in the
@@ -57,20 +58,7 @@ constexpr int kWave = 64;
 #ifndef W2V_EXP_SKIP
 #define W2V_EXP_SKIP 0
 #endif
-// Largest workgroup per row width: up to 16 waves share one LDS region of
-// privatised rows while the register budget (<=128 VGPRs at 4 waves/SIMD)
-// holds; wider rows keep 4-wave workgroups.
-template <int NV>
-constexpr int kMaxBlock = NV <= 6 ? 1024 : 256;
-// Waves per SIMD the epoch kernel is compiled for: two 16-wave workgroups per
-// CU when a row is <= 2 floats per lane (d <= 128: 64 VGPRs), else one.
-#ifndef W2V_MIN_WAVES
-template <int NV>
-constexpr int kMinWaves = NV <= 2 ? 8 : NV <= 16 ? 4 : 2;  // d > 1024: 256 VGPRs
-#else  // occupancy experiments (tools/r02/occ_probe.sh)
-template <int NV>
-constexpr int kMinWaves = W2V_MIN_WAVES;
-#endif
+// (kMaxBlock, kMinWaves and the other limits the launch policy shares: w2v_limits.hpp)
 
 struct TrainArgs {
   float* W;
@@ -130,14 +118,6 @@ struct TrainArgs {
   float priv_sc[128];          // kPrivMax
   float ctx_sc[64];            // kCtxMax
 };
-
-// LDS the shared-negatives kernel gives its row slots (w2v_shared.hpp kSnPriv; <= 32 rows):
-// 20 KiB = 10 rows at d = 512 with four 2-wave workgroups per CU (38.9 KiB each).
-#ifndef W2V_SN_PRIV_BYTES
-constexpr int kSnPrivBytes = 20 * 1024;
-#else  // experiments (tools/r02/sn_slots_probe.sh)
-constexpr int kSnPrivBytes = W2V_SN_PRIV_BYTES;
-#endif
 
 struct Counters {
   unsigned long long centers = 0, contexts = 0, targets = 0, draws = 0, sentences = 0;
@@ -234,11 +214,8 @@ __device__ __forceinline__ uint32_t philox_table_pos(const TrainArgs& a, uint32_
 //   output rows, [13, 15) of the context rows (W2V_PRIV_ADD 2), then (from
 //   lds_header_words) the pending deltas: priv_n output rows, then ctx_n
 //   context rows, NV * 64 floats each. The output range holds at most
-//   kPrivMax rows, the context range kCtxMax.
+//   kPrivMax rows, the context range kCtxMax (w2v_limits.hpp).
 // ---------------------------------------------------------------------------
-constexpr int kPrivMax = 128;
-constexpr int kCtxMax = 64;
-__host__ __device__ inline int64_t lds_header_words(int64_t, int64_t) { return 16; }
 
 struct PrivRows {  // one privatised row range [lo, lo + n) of matrix M (n == 0: none)
   float* delta = nullptr;
@@ -1402,16 +1379,8 @@ __device__ __forceinline__ void cbow_center_wide(const TrainArgs& a, float* lds,
                                       rp, cnt, lane);
 }
 
-constexpr int kWideChunks = 4;  // wide-window CBOW kernels: window <= 32 * kWideChunks - 1 in registers
-constexpr int kMaxWideWindow = 32 * kWideChunks - 1;
-// Any larger window (the reference takes any, Word2Vec.cpp:285): cbow_center_huge.
+// Any window past kMaxWideWindow (the reference takes any, Word2Vec.cpp:285): cbow_center_huge.
 constexpr int kMaxWindow = (1 << 20) - 1;
-// Ints of a wave's cbow_center_huge scratch slice for `window`: the unique
-// ids (<= 2 window) and one 64-bit unique mask per 64 span positions.
-__host__ __device__ inline int64_t huge_stride(int window) {
-  const int64_t span = 2 * (int64_t)window + 1;
-  return 2 * (int64_t)window + 2 * ((span + 63) / 64) + 2;
-}
 
 // CBOW center for windows past kMaxWideWindow: the same set semantics and
 // ascending visiting order as cbow_center, with the span read from the
@@ -1634,7 +1603,6 @@ __global__ __launch_bounds__(kMaxBlock<NV>, kMinWaves<NV>) void train_epoch_kern
 // trips. Same arithmetic in the same order as train_epoch_kernel.
 template <int NV>
 constexpr int kDeepMaxT = NV <= 2 ? 32 : NV <= 4 ? 24 : NV <= 6 ? 16 : NV <= 16 ? 8 : 4;
-constexpr int kDeepBlock = 256;
 template <int NV, int MAXT, bool CBOW, bool HS, bool NS, bool REPLAY, bool WIDE>
 __global__ __launch_bounds__(kDeepBlock, 2) void train_epoch_deep_kernel(TrainArgs a) {
   train_epoch<NV, MAXT, CBOW, HS, NS, REPLAY, WIDE>(a);

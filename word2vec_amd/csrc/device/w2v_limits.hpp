@@ -1,0 +1,58 @@
+// w2v_limits.hpp — the limits the kernels (w2v_kernels.hpp, w2v_shared.hpp)
+// and the launch policy (w2v_policy.cpp) share. No HIP header: the policy is
+// compiled by the host compiler too.
+#pragma once
+#include <stdint.h>
+
+#ifdef __HIPCC__
+#define W2V_HD __host__ __device__
+#else
+#define W2V_HD
+#endif
+
+namespace w2v {
+
+constexpr int kWave = 64;
+// Largest workgroup per row width: up to 16 waves share one LDS region of
+// privatised rows while the register budget (<=128 VGPRs at 4 waves/SIMD)
+// holds; wider rows keep 4-wave workgroups.
+constexpr int max_block(int nv) { return nv <= 6 ? 1024 : 256; }
+template <int NV>
+constexpr int kMaxBlock = max_block(NV);
+// Waves per SIMD the epoch kernel is compiled for: two 16-wave workgroups per
+// CU when a row is <= 2 floats per lane (d <= 128: 64 VGPRs), else one.
+#ifndef W2V_MIN_WAVES
+constexpr int min_waves(int nv) { return nv <= 2 ? 8 : nv <= 16 ? 4 : 2; }  // d > 1024: 256 VGPRs
+#else  // occupancy experiments (tools/r02/occ_probe.sh)
+constexpr int min_waves(int) { return W2V_MIN_WAVES; }
+#endif
+template <int NV>
+constexpr int kMinWaves = min_waves(NV);
+
+// LDS the shared-negatives kernel gives its row slots (w2v_shared.hpp kSnPriv; <= 32 rows):
+// 20 KiB = 10 rows at d = 512 with four 2-wave workgroups per CU (38.9 KiB each).
+#ifndef W2V_SN_PRIV_BYTES
+constexpr int kSnPrivBytes = 20 * 1024;
+#else  // experiments (tools/r02/sn_slots_probe.sh)
+constexpr int kSnPrivBytes = W2V_SN_PRIV_BYTES;
+#endif
+
+// LDS-privatised rows of the per-pair kernel (layout: w2v_kernels.hpp): the
+// output range holds at most kPrivMax rows, the context range kCtxMax.
+constexpr int kPrivMax = 128;
+constexpr int kCtxMax = 64;
+W2V_HD inline int64_t lds_header_words(int64_t, int64_t) { return 16; }
+
+constexpr int kWideChunks = 4;  // wide-window CBOW kernels: window <= 32 * kWideChunks - 1 in registers
+constexpr int kMaxWideWindow = 32 * kWideChunks - 1;
+// Ints of a wave's cbow_center_huge scratch slice for `window`: the unique
+// ids (<= 2 window) and one 64-bit unique mask per 64 span positions.
+W2V_HD inline int64_t huge_stride(int window) {
+  const int64_t span = 2 * (int64_t)window + 1;
+  return 2 * (int64_t)window + 2 * ((span + 63) / 64) + 2;
+}
+
+// Workgroup size of train_epoch_deep_kernel.
+constexpr int kDeepBlock = 256;
+
+}  // namespace w2v

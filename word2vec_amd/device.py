@@ -248,6 +248,20 @@ class DeviceTrainer:
                 "flush_centers": f.value, "context_flush": cf.value, "hot_tau_rows": tr.value,
                 "private_rate": round(mu.value, 4), "wave_cap": wc.value, "deep": dp.value}
 
+    def launch_plan(self) -> dict:
+        """Everything the last launch's policy decided (w2v_dev_launch_plan). The scale arrays come back as
+        float32 numpy arrays: priv_sc (128), ctx_sc (64), hot_sc (one per scaled atomic hot Huffman node)."""
+        p = N.LaunchPlan()
+        self._chk(self.lib.w2v_dev_launch_plan(self.h, C.byref(p), None, 0), "w2v_dev_launch_plan")  # the count
+        hot = np.zeros(p.n_hot_sc, np.float32)
+        if hot.size:
+            buf = hot.ctypes.data_as(C.POINTER(C.c_float))
+            self._chk(self.lib.w2v_dev_launch_plan(self.h, C.byref(p), buf, hot.size), "w2v_dev_launch_plan")
+        skip = ("n_hot_sc", "priv_sc", "ctx_sc")
+        out = {k: getattr(p, k) for k, _ in p._fields_ if k not in skip}
+        out.update(priv_sc=np.array(p.priv_sc, np.float32), ctx_sc=np.array(p.ctx_sc, np.float32), hot_sc=hot)
+        return out
+
     def set_private_rows(self, n: int):
         """Hottest output rows privatised per workgroup in LDS: -1 auto (default), 0 off."""
         self._chk(self.lib.w2v_dev_set_private_rows(self.h, int(n)), "w2v_dev_set_private_rows")
