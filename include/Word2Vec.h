@@ -17,6 +17,7 @@
 #include <random>
 #include <string>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "Word.h"
@@ -229,6 +230,32 @@ class Word2Vec {
   // max |M_i - M_0| / max |M_0| (w2v_dev_model_max_diff; -1 = not measured).
   int64_t replica_rounds = 0;
   double replica_max_diff = -1.0;
+  // Nearest neighbours of a combination of words among the rows of W (cosine,
+  // gensim's most_similar; word2vec's distance and word-analogy): the topn
+  // words nearest sum(unit positive rows) - sum(unit negative rows), best
+  // first (equal scores: the more frequent word first), never one of the
+  // query's own words, among the restrict_vocab most frequent words (0 = all).
+  // analogy(a, b, c) answers a : b :: c : ? = most_similar({b, c}, {a}). The
+  // scores come from the device (include/w2v_dev.h, w2v_nn_*) over an index
+  // built from the host W on first use: after train() and equally after
+  // load_word2vec(), no vocabulary product needed. At most 8 words per query,
+  // topn <= 64; an unknown word, too many words or a device failure sets
+  // last_error and throws std::runtime_error. The index is cached and dropped
+  // by every member that can change W (train*, init_weights, load_word2vec,
+  // load_checkpoint, train_sentence_*, negative_sampling,
+  // hierarchical_softmax); code that writes the public W directly calls
+  // drop_index() afterwards.
+  std::vector<std::pair<std::string, float>> most_similar(const std::vector<std::string>& positive,
+                                                          const std::vector<std::string>& negative, int topn = 10,
+                                                          int64_t restrict_vocab = 0);
+  std::vector<std::pair<std::string, float>> analogy(const std::string& a, const std::string& b,
+                                                     const std::string& c, int topn = 1, int64_t restrict_vocab = 0);
+  // The same by vocabulary index (w2v_nn_query_rows for one query: ids[t] = -1
+  // skips a term): out_ids / out_scores take k entries, -1 / -inf past the
+  // last candidate.
+  void most_similar_ids(const int32_t* ids, const float* weights, int terms, int64_t restrict_vocab, int k,
+                        int32_t* out_ids, float* out_scores);
+  void drop_index();
   // Last device error (empty if none).
   std::string last_error;
 
@@ -251,6 +278,7 @@ class Word2Vec {
   std::string generator_state() const;
   void restore_generator(const std::string& state);
   bool continues_schedule() const;
+  w2v_nn* nn_ = nullptr;            // most_similar: the cached index over W
   w2v_ingest* ingest_ = nullptr;    // gpu_ingest: the counted file ...
   std::string ingest_key_;          //   ... (path + format)
   std::vector<std::string> ingest_words_;  // its distinct words, in order of first occurrence

@@ -472,6 +472,58 @@ int w2v_group_average_rows_async(w2v_group* g, int64_t rows);
 int w2v_group_finish(w2v_group* g);
 int w2v_group_info(w2v_group* g, int32_t* nranks, int32_t* local, int32_t* overlap, int64_t* rounds);
 
+/* ---------------------------------------------------------------------------
+ * Nearest-neighbour and analogy queries (new: the reference has no query side;
+ * word2vec's distance / word-analogy / compute-accuracy). An index holds a
+ * row-major fp32 matrix on the device and inv_norm[r] = 1 / max(|row r|, 1e-12);
+ * a query returns, per query vector, the k rows of highest cosine (the unit
+ * query against the unit row), ordered by score descending and then by row id
+ * ascending. The scores are an exact-f32 GEMM on the matrix cores with the
+ * top-k fused behind it: the queries x rows score matrix never reaches memory
+ * (DESIGN.md §4.4). Excluded rows, rows at or past restrict_rows and
+ * non-finite scores are never returned; slots past the number of candidates
+ * hold id -1 and score -inf. A row's score does not depend on the strip count
+ * or the launch: duplicate rows tie bit-exactly, and the same call returns the
+ * same bits every time. All calls are synchronous and validate their
+ * arguments before any device call. Limits: dim <= 2048, k <= 64, terms <= 8.
+ *
+ * w2v_nn_create copies `rows` (host, n_rows x dim dense) to `device` (-1 = the
+ * calling thread's current one). w2v_nn_attach borrows the resident W
+ * (which 0) or C (1) of a handle instead, with no copy: it first waits for the
+ * work enqueued on the handle's stream. After training moved the matrix,
+ * w2v_nn_refresh (which waits the same way) recomputes inv_norm; queries
+ * between the two see the new rows with stale norms. An attached index never
+ * frees the matrix and must be destroyed before the handle is: destroying the
+ * handle first is the caller's error.
+ *
+ * w2v_nn_query_vectors: q holds nq host vectors of dim floats of any length
+ * (they are scaled to unit length; a zero vector scores 0 against every row);
+ * exclude, when not NULL, holds n_excl row ids per query that it must not
+ * return (-1 = none). w2v_nn_query_rows builds each query from the index's own
+ * rows, q = sum_t weights[t] * row[ids[t]] / |row[ids[t]]| (ids[t] = -1 skips
+ * a term), and never returns a query's own term ids: the single word (terms 1,
+ * weight 1), the analogy a : b :: c : ? (ids (b, a, c), weights (1, -1, 1)),
+ * positive and negative word sets (weights +1 / -1).
+ *
+ * The candidate rows are cut into strips; w2v_nn_set_strip_rows sets the rows
+ * per strip (0 = automatic, up to 16 MiB of rows; otherwise a multiple of 16;
+ * the answer does not depend on it; a query whose strips x k partial lists of
+ * one query block would pass 512 MiB is refused with W2V_ERR_ARG) and w2v_nn_plan reports the strips, the
+ * queries per workgroup and the rows per strip of the last query.
+ * ------------------------------------------------------------------------- */
+typedef struct w2v_nn w2v_nn;
+int w2v_nn_limits(int32_t* max_dim, int32_t* max_k, int32_t* max_terms);
+int w2v_nn_create(int32_t device, const float* rows, int64_t n_rows, int32_t dim, w2v_nn** out);
+int w2v_nn_attach(w2v_dev* h, int32_t which, w2v_nn** out);
+int w2v_nn_refresh(w2v_nn* x);
+void w2v_nn_destroy(w2v_nn* x);
+int w2v_nn_set_strip_rows(w2v_nn* x, int64_t rows);
+int w2v_nn_plan(w2v_nn* x, int64_t* strips, int32_t* query_block, int64_t* strip_rows);
+int w2v_nn_query_vectors(w2v_nn* x, const float* q, int64_t nq, const int32_t* exclude, int32_t n_excl,
+                         int64_t restrict_rows, int32_t k, int32_t* out_ids, float* out_scores);
+int w2v_nn_query_rows(w2v_nn* x, const int32_t* ids, const float* weights, int32_t terms, int64_t nq,
+                      int64_t restrict_rows, int32_t k, int32_t* out_ids, float* out_scores);
+
 #ifdef __cplusplus
 }
 #endif

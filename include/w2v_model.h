@@ -80,6 +80,26 @@ int w2v_model_train_sentence(w2v_model* m, const int32_t* ids, int64_t n, float 
 int w2v_model_negative_sampling(w2v_model* m, int64_t word, float* x, float* grad, int32_t which, float alpha);
 int w2v_model_hierarchical_softmax(w2v_model* m, int64_t word, float* x, float* grad, float alpha);
 
+/* Word2Vec::most_similar by vocabulary index: the k rows of W nearest (cosine)
+ * sum_t weights[t] * unit(W[ids[t]]) (ids[t] = -1 skips a term; terms <= 8,
+ * k <= 64), best first, never one of the query's own ids, among rows
+ * [0, restrict_rows) (0 = all). out_ids / out_scores take k entries (-1 / -inf past
+ * the last candidate). The analogy a : b :: c : ? is ids (b, a, c), weights
+ * (1, -1, 1). The scores come from the device (include/w2v_dev.h w2v_nn_*); the
+ * index over W is cached until a call that can change W (w2v_model_set_matrix
+ * included). */
+int w2v_model_most_similar(w2v_model* m, const int64_t* ids, const float* weights, int32_t terms,
+                           int64_t restrict_rows, int32_t k, int32_t* out_ids, float* out_scores);
+/* Word2Vec::most_similar / Word2Vec::analogy by word: positive and negative
+ * are whitespace-separated words (NULL or "" = none). The answers come back as
+ * vocabulary indices (w2v_model_word names them) with their scores, best
+ * first: *n_out entries (<= topn) of out_ids / out_scores, which take topn.
+ * An unknown word is an error (non-zero, last_error names the word). */
+int w2v_model_most_similar_words(w2v_model* m, const char* positive, const char* negative, int32_t topn,
+                                 int64_t restrict_rows, int32_t* out_ids, float* out_scores, int32_t* n_out);
+int w2v_model_analogy(w2v_model* m, const char* a, const char* b, const char* c, int32_t topn,
+                      int64_t restrict_rows, int32_t* out_ids, float* out_scores, int32_t* n_out);
+
 int w2v_model_save(w2v_model* m, const char* path, int32_t which, int32_t binary);
 int w2v_model_load(w2v_model* m, const char* path, int32_t binary);
 int w2v_model_save_vocab(w2v_model* m, const char* path);

@@ -159,6 +159,16 @@ SIGNATURES = {
     "w2v_group_average_rows_async": (C.c_int, [_P, _I64]),
     "w2v_group_finish": (C.c_int, [_P]),
     "w2v_group_info": (C.c_int, [_P, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I64)]),
+    # nearest-neighbour queries (w2v_nn_*)
+    "w2v_nn_limits": (C.c_int, [C.POINTER(_I32)] * 3),
+    "w2v_nn_create": (C.c_int, [_I32, _P, _I64, _I32, C.POINTER(_P)]),
+    "w2v_nn_attach": (C.c_int, [_P, _I32, C.POINTER(_P)]),
+    "w2v_nn_refresh": (C.c_int, [_P]),
+    "w2v_nn_destroy": (None, [_P]),
+    "w2v_nn_set_strip_rows": (C.c_int, [_P, _I64]),
+    "w2v_nn_plan": (C.c_int, [_P, C.POINTER(_I64), C.POINTER(_I32), C.POINTER(_I64)]),
+    "w2v_nn_query_vectors": (C.c_int, [_P, _P, _I64, _P, _I32, _I64, _I32, _P, _P]),
+    "w2v_nn_query_rows": (C.c_int, [_P, _P, _P, _I32, _I64, _I64, _I32, _P, _P]),
     # include/w2v_ingest.h
     "w2v_ingest_create": (C.c_int, [_I32, _I32, _I64, C.POINTER(_P)]),
     "w2v_ingest_destroy": (None, [_P]),

@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <fstream>
 #include <random>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -117,7 +118,26 @@ int main(int argc, char** argv) {
     expect(w2v_model_train_sentence(m, bad, 2, 0.01f, 0) != 0, "train_sentence bad id rejected");
     float x[16] = {0}, g[16] = {0};
     expect(w2v_model_negative_sampling(m, 1 << 30, x, g, 1, 0.01f) != 0, "negative_sampling bad id rejected");
+    // most_similar / analogy: an unknown word is refused before any device call
+    int32_t oi[4];
+    float os[4];
+    int32_t on = -1;
+    expect(w2v_model_most_similar_words(m, "w0 no-such-word", "w1", 4, 0, oi, os, &on) != 0, "most_similar unknown word");
+    expect(std::string(w2v_model_last_error(m)).find("no-such-word") != std::string::npos, "the error names the word");
+    expect(w2v_model_analogy(m, "w0", "w1", "no-such-word", 1, 0, oi, os, &on) != 0, "analogy unknown word");
+    expect(w2v_model_most_similar_words(m, "w0", "", 4, 0, nullptr, os, &on) != 0, "most_similar null output");
     w2v_model_free(m);
+  }
+  {  // the class members themselves: last_error and the exception
+    Word2Vec w(1, 5, 2, 20000, 16, 5, 1e-3f, 0.025f, 1e-6f, true, 1, "ns", "sg");
+    w.build_vocab(sents);
+    bool threw = false;
+    try {
+      w.analogy("w0", "w1", "no-such-word");
+    } catch (const std::runtime_error&) {
+      threw = true;
+    }
+    expect(threw && w.last_error.find("no-such-word") != std::string::npos, "Word2Vec::analogy unknown word");
   }
   std::printf("host selftest: %d failure(s)\n", failures);
   return failures ? 1 : 0;

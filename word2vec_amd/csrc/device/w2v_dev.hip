@@ -169,7 +169,7 @@ struct w2v_dev {
 
 namespace w2v {
 int set_error(int code, const std::string& msg) { return fail(code, msg); }
-DevInfo dev_info(const w2v_dev* h) { return DevInfo{h->device, h->stream, h->V}; }
+DevInfo dev_info(const w2v_dev* h) { return DevInfo{h->device, h->stream, h->V, h->cfg.word_dim}; }
 void set_replicas(w2v_dev* h, int32_t n) { h->replicas = n < 1 ? 1 : n; }
 }  // namespace w2v
 

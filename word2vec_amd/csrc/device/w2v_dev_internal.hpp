@@ -20,6 +20,7 @@ struct DevInfo {
   int device;
   hipStream_t stream;
   int64_t V;
+  int dim;  // word_dim
 };
 DevInfo dev_info(const w2v_dev* h);
 // The replicas of the exchange group a handle joined (w2v_group_create: all

@@ -29,6 +29,7 @@ bool count_desc(Word* a, Word* b) { return a->count > b->count; }  // Word2Vec.c
 }  // namespace
 
 Word2Vec::~Word2Vec(void) {
+  drop_index();
   if (ingest_) w2v_ingest_destroy(ingest_);
   if (dev_) w2v_dev_destroy(dev_);
 }
@@ -252,6 +253,7 @@ bool Word2Vec::uses_C() const { return negative > 0 || model == "cbow"; }
 // it. For cbow + hs, C (the CBOW input matrix) is drawn like W right after it:
 // the reference reads an unallocated C there (documented deviation).
 void Word2Vec::init_weights(size_t vocab_size) {
+  drop_index();
   std::uniform_real_distribution<float> dist(-0.5, 0.5);
   const size_t d = (size_t)word_dim;
   W.resize((w2v_dense::Index)vocab_size, (w2v_dense::Index)d);
@@ -695,6 +697,7 @@ void Word2Vec::check_limits() const {
 // Word2Vec.cpp:356-396.
 void Word2Vec::train(std::vector<std::vector<std::string>>& sentences) {
   check_limits();
+  drop_index();
   if (!resume_) init_weights(vocab.size());
   int64_t train_words = 0;
   for (auto& s : sentences) train_words += (int64_t)s.size();
@@ -713,6 +716,7 @@ void Word2Vec::train(std::vector<std::vector<std::string>>& sentences) {
 void Word2Vec::train_ids(const std::vector<int32_t>& ids, const std::vector<int64_t>& offsets,
                          int64_t train_words) {
   check_limits();
+  drop_index();
   if (!resume_) init_weights(vocab.size());
   run_epochs(ids, offsets, train_words);
 }
@@ -722,6 +726,7 @@ void Word2Vec::train_ids(const std::vector<int32_t>& ids, const std::vector<int6
 // ---------------------------------------------------------------------------
 void Word2Vec::apply_rows(RMatrixXf& M, int, const std::vector<size_t>& rows, const std::vector<uint8_t>& codes,
                           RowVectorXf& x, RowVectorXf& grad, float alpha, bool hs_form) {
+  drop_index();  // M may be W
   ensure_device();
   const size_t d = (size_t)word_dim, n = rows.size();
   std::vector<float> buf(n * d);
@@ -766,6 +771,7 @@ RowVectorXf& Word2Vec::negative_sampling(Word* predict_word, RowVectorXf& projec
 // sentence words' Huffman paths — O(touched rows x dim) per call, as the
 // reference's own update, instead of the whole V x dim model.
 void Word2Vec::train_one_sentence(std::vector<Word*>& sentence, float alpha, bool cbow) {
+  drop_index();
   const std::string saved = model;
   model = cbow ? "cbow" : "sg";
   try {
@@ -835,6 +841,53 @@ void Word2Vec::train_sentence_sg(std::vector<Word*>& sentence, float alpha) {
 }
 
 // ---------------------------------------------------------------------------
+// Queries (additive): nearest neighbours of word combinations among the rows
+// of W, scored on the device (include/w2v_dev.h, w2v_nn_*).
+// ---------------------------------------------------------------------------
+void Word2Vec::drop_index() {
+  if (nn_) w2v_nn_destroy(nn_);
+  nn_ = nullptr;
+}
+
+void Word2Vec::most_similar_ids(const int32_t* ids, const float* weights, int terms, int64_t restrict_vocab, int k,
+                                int32_t* out_ids, float* out_scores) {
+  if (!nn_)
+    check(w2v_nn_create(gpu_device, W.data(), (int64_t)W.rows(), (int32_t)W.cols(), &nn_), "most_similar (w2v_nn_create)");
+  check(w2v_nn_query_rows(nn_, ids, weights, terms, 1, restrict_vocab, k, out_ids, out_scores),
+        "most_similar (w2v_nn_query_rows)");
+}
+
+std::vector<std::pair<std::string, float>> Word2Vec::most_similar(const std::vector<std::string>& positive,
+                                                                  const std::vector<std::string>& negative, int topn,
+                                                                  int64_t restrict_vocab) {
+  std::vector<int32_t> ids;
+  std::vector<float> weights;
+  for (int sign = 0; sign < 2; ++sign) {
+    for (const std::string& text : sign == 0 ? positive : negative) {
+      auto it = vocab_hash.find(text);
+      if (it == vocab_hash.end()) {
+        last_error = "most_similar: '" + text + "' is not in the vocabulary";
+        throw std::runtime_error("word2vec_amd: " + last_error);
+      }
+      ids.push_back((int32_t)it->second->index);
+      weights.push_back(sign == 0 ? 1.0f : -1.0f);
+    }
+  }
+  std::vector<int32_t> out_ids((size_t)std::max(topn, 1), -1);
+  std::vector<float> out_scores((size_t)std::max(topn, 1), 0.0f);
+  most_similar_ids(ids.data(), weights.data(), (int)ids.size(), restrict_vocab, topn, out_ids.data(), out_scores.data());
+  std::vector<std::pair<std::string, float>> out;
+  for (int j = 0; j < topn && out_ids[(size_t)j] >= 0; ++j)
+    out.emplace_back(vocab[(size_t)out_ids[(size_t)j]]->text, out_scores[(size_t)j]);
+  return out;
+}
+
+std::vector<std::pair<std::string, float>> Word2Vec::analogy(const std::string& a, const std::string& b,
+                                                             const std::string& c, int topn, int64_t restrict_vocab) {
+  return most_similar({b, c}, {a}, topn, restrict_vocab);
+}
+
+// ---------------------------------------------------------------------------
 // Vector files (Word2Vec.cpp:398-495), same bytes.
 // ---------------------------------------------------------------------------
 void Word2Vec::save_word2vec(std::string filename, const RMatrixXf& data, bool binary) {
@@ -862,6 +915,7 @@ void Word2Vec::save_word2vec(std::string filename, const RMatrixXf& data, bool b
 }
 
 void Word2Vec::load_word2vec(std::string filename, bool binary) {
+  drop_index();
   if (W.rows() != (RMatrixXf::Index)vocab.size() || W.cols() != word_dim)
     W.resize((RMatrixXf::Index)vocab.size(), word_dim);
   if (binary) {
@@ -1006,6 +1060,7 @@ bool Word2Vec::continues_schedule() const {
 }
 
 void Word2Vec::load_checkpoint(const std::string& path) {
+  drop_index();
   std::ifstream in(path, std::ios::binary);
   if (!in) throw std::runtime_error("checkpoint: cannot read " + path);
   char magic[8];

@@ -208,9 +208,65 @@ int w2v_model_set_matrix(w2v_model* m, int32_t which, const float* in, int64_t r
              std::to_string(rows) + " x " + std::to_string(cols);
     return 1;
   }
+  m->w.drop_index();
   M->resize((RMatrixXf::Index)rows, m->w.word_dim);
   std::memcpy(M->data(), in, sizeof(float) * (size_t)M->size());
   return 0;
+}
+
+int w2v_model_most_similar(w2v_model* m, const int64_t* ids, const float* weights, int32_t terms, int64_t restrict_rows,
+                           int32_t k, int32_t* out_ids, float* out_scores) {
+  return guard(m, [&] {
+    if (!ids || !weights || !out_ids || !out_scores) throw std::invalid_argument("most_similar: null argument");
+    std::vector<int32_t> i32;
+    for (int32_t t = 0; t < terms; ++t) {
+      if (ids[t] >= (int64_t)m->w.W.rows()) throw std::out_of_range("most_similar: row id outside W");
+      i32.push_back(ids[t] < 0 ? -1 : (int32_t)ids[t]);
+    }
+    m->w.most_similar_ids(i32.data(), weights, terms, restrict_rows, k, out_ids, out_scores);
+  });
+}
+
+namespace {
+
+std::vector<std::string> split_words(const char* text) {
+  std::vector<std::string> out;
+  std::istringstream toks(text ? text : "");
+  std::string t;
+  while (toks >> t) out.push_back(t);
+  return out;
+}
+
+// Word2Vec::most_similar's (word, score) pairs as vocabulary indices.
+void copy_answers(w2v_model* m, const std::vector<std::pair<std::string, float>>& got, int32_t topn, int32_t* out_ids,
+                  float* out_scores, int32_t* n_out) {
+  int32_t n = 0;
+  for (const auto& ws : got) {
+    if (n >= topn) break;
+    out_ids[n] = (int32_t)m->w.vocab_hash.at(ws.first)->index;
+    out_scores[n] = ws.second;
+    ++n;
+  }
+  if (n_out) *n_out = n;
+}
+
+}  // namespace
+
+int w2v_model_most_similar_words(w2v_model* m, const char* positive, const char* negative, int32_t topn,
+                                 int64_t restrict_rows, int32_t* out_ids, float* out_scores, int32_t* n_out) {
+  return guard(m, [&] {
+    if (!out_ids || !out_scores) throw std::invalid_argument("most_similar: null output");
+    copy_answers(m, m->w.most_similar(split_words(positive), split_words(negative), topn, restrict_rows), topn,
+                 out_ids, out_scores, n_out);
+  });
+}
+
+int w2v_model_analogy(w2v_model* m, const char* a, const char* b, const char* c, int32_t topn, int64_t restrict_rows,
+                      int32_t* out_ids, float* out_scores, int32_t* n_out) {
+  return guard(m, [&] {
+    if (!a || !b || !c || !out_ids || !out_scores) throw std::invalid_argument("analogy: null argument");
+    copy_answers(m, m->w.analogy(a, b, c, topn, restrict_rows), topn, out_ids, out_scores, n_out);
+  });
 }
 
 int w2v_model_train_sentence(w2v_model* m, const int32_t* ids, int64_t n, float alpha, int32_t cbow) {

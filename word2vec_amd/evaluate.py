@@ -43,14 +43,20 @@ def read_similarity(path) -> list[tuple[str, str, float]]:
 
 
 def analogy_accuracy(words: list[str], vecs: np.ndarray, questions, restrict: int | None = None,
-                     lowercase: bool = False, batch: int = 1024) -> dict:
+                     lowercase: bool = False, batch: int = 1024, index=None) -> dict:
     """3CosAdd: argmax_x cos(x, b - a + c) over the vocabulary (the first
-    `restrict` words if given), excluding a, b, c. Returns accuracy in percent."""
+    `restrict` words if given), excluding a, b, c. Returns accuracy in percent.
+
+    index: a word2vec_amd.nn.NearestIndex over `vecs` (same rows, same order).
+    The argmax then comes from the GPU (query_rows, k = 1) instead of the dense
+    numpy score matrix, and `vecs` is not read. None (the default) is the
+    numpy path."""
     idx = {}
     for i, w in enumerate(words):
         idx.setdefault(w.lower() if lowercase else w, i)
-    E = normalize(vecs)
-    cand = E if restrict is None else E[:restrict]
+    if index is None:
+        E = normalize(vecs)
+        cand = E if restrict is None else E[:restrict]
     q = []
     for a, b, c, d in questions:
         key = [x.lower() if lowercase else x for x in (a, b, c, d)]
@@ -61,6 +67,13 @@ def analogy_accuracy(words: list[str], vecs: np.ndarray, questions, restrict: in
     if not q:
         return {"accuracy": 0.0, "correct": 0, "answered": 0, "skipped": len(questions)}
     Q = np.array(q, dtype=np.int64)
+    if index is not None:
+        qa, qb, qc, qd = Q.T
+        best, _ = index.query_rows(np.stack([qb, qa, qc], axis=1), (1.0, -1.0, 1.0), k=1,
+                                   restrict=0 if restrict is None else int(restrict))
+        correct = int((best[:, 0] == qd).sum())  # every candidate excluded -> id -1 -> wrong
+        return {"accuracy": 100.0 * correct / len(Q), "correct": correct, "answered": int(len(Q)),
+                "skipped": len(questions) - int(len(Q))}
     correct = 0
     for s in range(0, len(Q), batch):
         qa, qb, qc, qd = Q[s:s + batch].T

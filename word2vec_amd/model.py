@@ -59,6 +59,9 @@ def _load():
             "w2v_model_train_sentence": (C.c_int, [P, P, I64, F, I32]),
             "w2v_model_negative_sampling": (C.c_int, [P, I64, P, P, I32, F]),
             "w2v_model_hierarchical_softmax": (C.c_int, [P, I64, P, P, F]),
+            "w2v_model_most_similar": (C.c_int, [P, P, P, I32, I64, I32, P, P]),
+            "w2v_model_most_similar_words": (C.c_int, [P, S, S, I32, I64, P, P, C.POINTER(I32)]),
+            "w2v_model_analogy": (C.c_int, [P, S, S, S, I32, I64, P, P, C.POINTER(I32)]),
             "w2v_model_save": (C.c_int, [P, S, I32, I32]),
             "w2v_model_load": (C.c_int, [P, S, I32]),
             "w2v_model_save_vocab": (C.c_int, [P, S]),
@@ -250,6 +253,38 @@ class Word2Vec:
 
     def precalc_sampling(self):
         self._chk(self.L.w2v_model_precalc_sampling(self.h), "precalc_sampling")
+
+    def most_similar_ids(self, ids, weights=None, k=10, restrict=0):
+        """Word2Vec::most_similar by vocabulary index: (ids int32 [k], scores float32 [k]) of the rows of W
+        nearest sum_t weights[t] * unit(W[ids[t]]), scored on the GPU (include/w2v_model.h)."""
+        ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
+        w = np.ones(ids.size, np.float32) if weights is None else np.ascontiguousarray(weights, np.float32).reshape(-1)
+        if w.size != ids.size:
+            raise ValueError("most_similar_ids: one weight per id")
+        out = np.empty(max(int(k), 0), np.int32)
+        sc = np.empty(max(int(k), 0), np.float32)
+        self._chk(self.L.w2v_model_most_similar(self.h, _p(ids), _p(w), ids.size, int(restrict), int(k), _p(out),
+                                                _p(sc)), "most_similar")
+        return out, sc
+
+    def _answers(self, call, topn):
+        out = np.empty(max(int(topn), 1), np.int32)
+        sc = np.empty(max(int(topn), 1), np.float32)
+        n = C.c_int32()
+        self._chk(call(_p(out), _p(sc), C.byref(n)), "most_similar")
+        return [(self.L.w2v_model_word(self.h, int(i)).decode("utf-8", errors="surrogateescape"), float(s))
+                for i, s in zip(out[:n.value], sc[:n.value])]
+
+    def most_similar(self, positive=(), negative=(), topn=10, restrict_vocab=0):
+        """Word2Vec::most_similar: [(word, cosine)] nearest sum unit(positive) - sum unit(negative), best first."""
+        pos, neg = " ".join(positive).encode(), " ".join(negative).encode()
+        return self._answers(lambda o, s, n: self.L.w2v_model_most_similar_words(
+            self.h, pos, neg, int(topn), int(restrict_vocab), o, s, n), topn)
+
+    def analogy(self, a, b, c, topn=1, restrict_vocab=0):
+        """Word2Vec::analogy: a is to b as c is to ...; [(word, cosine)]."""
+        return self._answers(lambda o, s, n: self.L.w2v_model_analogy(
+            self.h, a.encode(), b.encode(), c.encode(), int(topn), int(restrict_vocab), o, s, n), topn)
 
     # introspection ---------------------------------------------------------
     @property
