@@ -2,8 +2,8 @@
 gfx950 code objects the in-tree build leaves under word2vec_amd/lib/obj).
 
 The LDS-private rows' per-row lock (w2v_kernels.hpp priv_lock / priv_unlock,
-W2V_PRIV_ADD 2) is taken with a relaxed atomicOr and released with a relaxed
-atomicAnd; its correctness rests on those, and the row's reads and writes
+taken by priv_add and flush_private) is taken with a relaxed atomicOr and
+released with a relaxed atomicAnd; its correctness rests on those, and the row's reads and writes
 between them, being LDS instructions: one wave's LDS operations execute in
 issue order, so the release cannot overtake the row's writes (a
 generic pointer lowered to flat_* instructions would lose that ordering).

@@ -47,17 +47,6 @@
 
 namespace w2v {
 
-// Timing-only experiment builds (tools/r02/exp_variant.sh; never the product):
-// bit 1 skips the hot-row atomics of the targets, bit 2 the global atomics of
-// the private-row flushes, bit 4 the hot context-row atomics of CBOW; in the
-// shared-negatives kernel bit 8 skips the staged atomic rows, bit 16 the
-// private-row flush atomics, bit 32 makes the coherent (sc1) stores plain;
-// bit 64 skips the per-pair kernels' plain (Hogwild) row stores, bit 128
-// the LDS adds into the private rows' pending deltas, bit 256 the private
-// rows' pending-delta reads.
-#ifndef W2V_EXP_SKIP
-#define W2V_EXP_SKIP 0
-#endif
 // (kMaxBlock, kMinWaves and the other limits the launch policy shares: w2v_limits.hpp)
 
 struct TrainArgs {
@@ -137,11 +126,9 @@ struct Counters {
 
 // stats[kNonFinite] counts sigma arguments (row . input dot products) that
 // were not finite: the model diverged (w2v_dev_train_epoch returns
-// W2V_ERR_DIVERGED). Wave-uniform check, one atomic per offending update.
+// W2V_ERR_DIVERGED). Counted per batch of targets, one atomic per offending
+// batch (batch_grad_l).
 constexpr int kNonFinite = 5;
-__device__ __forceinline__ void note_nonfinite(unsigned long long* stats, bool bad, int lane) {
-  if (bad && lane == 0) atomicAdd(stats + kNonFinite, 1ull);
-}
 
 // ---------------------------------------------------------------------------
 // Wave primitives
@@ -211,10 +198,11 @@ __device__ __forceinline__ uint32_t philox_table_pos(const TrainArgs& a, uint32_
 // LDS-privatised rows of the per-pair kernel (when priv_n + ctx_n > 0), per workgroup:
 //   words [0,4) dirty mask of the output rows (2 x 64 bits), [4,8) of the
 //   context rows, [8] centers of the workgroup, [9, 13) lock bits of the
-//   output rows, [13, 15) of the context rows (W2V_PRIV_ADD 2), then (from
-//   lds_header_words) the pending deltas: priv_n output rows, then ctx_n
+//   output rows, [13, 15) of the context rows (priv_lock), then (from
+//   kLdsHeaderWords) the pending deltas: priv_n output rows, then ctx_n
 //   context rows, NV * 64 floats each. The output range holds at most
-//   kPrivMax rows, the context range kCtxMax (w2v_limits.hpp).
+//   kPrivMax rows, the context range kCtxMax. The offsets are the kLds*
+//   constants of w2v_limits.hpp.
 // ---------------------------------------------------------------------------
 
 struct PrivRows {  // one privatised row range [lo, lo + n) of matrix M (n == 0: none)
@@ -232,9 +220,9 @@ template <int NV>
 __device__ __forceinline__ PrivRows out_rows(const TrainArgs& a, float* lds) {
   PrivRows p;
   if (lds == nullptr || a.priv_n == 0) return p;
-  p.dirty = reinterpret_cast<unsigned long long*>(lds);
-  p.lock = reinterpret_cast<unsigned*>(lds) + 9;
-  p.delta = lds + lds_header_words(a.priv_n, a.ctx_n);
+  p.dirty = reinterpret_cast<unsigned long long*>(lds + kLdsDirtyOut);
+  p.lock = reinterpret_cast<unsigned*>(lds) + kLdsLockOut;
+  p.delta = lds + kLdsHeaderWords;
   p.M = const_cast<float*>(a.priv_M);
   p.lo = a.priv_lo;
   p.n = a.priv_n;
@@ -245,9 +233,9 @@ template <int NV>
 __device__ __forceinline__ PrivRows ctx_rows(const TrainArgs& a, float* lds) {
   PrivRows p;
   if (lds == nullptr || a.ctx_n == 0) return p;
-  p.dirty = reinterpret_cast<unsigned long long*>(lds + 4);
-  p.lock = reinterpret_cast<unsigned*>(lds) + 13;
-  p.delta = lds + lds_header_words(a.priv_n, a.ctx_n) + (int64_t)a.priv_n * (NV * kWave);
+  p.dirty = reinterpret_cast<unsigned long long*>(lds + kLdsDirtyCtx);
+  p.lock = reinterpret_cast<unsigned*>(lds) + kLdsLockCtx;
+  p.delta = lds + kLdsHeaderWords + (int64_t)a.priv_n * (NV * kWave);
   p.M = const_cast<float*>(a.ctx_M);
   p.lo = 0;
   p.n = a.ctx_n;
@@ -267,58 +255,24 @@ __device__ __forceinline__ PrivRows ctx_rows(const TrainArgs& a, float* lds) {
 // every store writes whole 128-B lines. The dot products add the padding's
 // zeros, so the sums are bit-identical to the guarded form.
 // ---------------------------------------------------------------------------
-#ifndef W2V_ROW_GUARDS  // timing experiments only (tools/r03): 1 = the per-element guards of round 2
-#define W2V_ROW_GUARDS 0
-#endif
-// W2V_ROW_BOUNDED: the row's last vector (the only one holding padding) goes
-// through a buffer resource whose range is the row's d floats: a lane past it
-// loads 0 and stores nothing WITHOUT an exec mask and without moving the
-// padding's bytes (d 100: 112 of a row's 512 B). Same values as the unbounded
-// form (the padding is zero). Measured (profiles/r03t_bounded_ab.log; parity
-// green): 0.2-0.3 % slower on configs[0]-[2] — the padding shares its 128-B
-// line with the row's last valid floats, so no line is saved. Off.
-#ifndef W2V_ROW_BOUNDED
-#define W2V_ROW_BOUNDED 0
-#endif
-constexpr int kBufSc1 = 16;  // buffer cache-policy bit sc1: device scope (bypasses the CU's L1)
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t row_rsrc(const float* base, int d) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, d * 4, 0x00020000);
-}
-
 template <int NV>
-__device__ __forceinline__ void load_row(const float* M, int64_t row, int64_t pitch, int d, int lane, bool fresh,
+__device__ __forceinline__ void load_row(const float* M, int64_t row, int64_t pitch, int lane, bool fresh,
                                          float (&r)[NV]) {
   const float* p = M + row * pitch + lane;
-  constexpr int NU = W2V_ROW_BOUNDED ? NV - 1 : NV;  // vectors loaded unbounded
   if (fresh) {  // agent-scope relaxed loads: global_load_dword sc1, bypass the CU's L1
 #pragma unroll
-    for (int v = 0; v < NU; ++v)
-      r[v] = (!W2V_ROW_GUARDS || lane + kWave * v < d)
-                 ? __hip_atomic_load(p + kWave * v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                 : 0.f;
+    for (int v = 0; v < NV; ++v) r[v] = __hip_atomic_load(p + kWave * v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   } else {
 #pragma unroll
-    for (int v = 0; v < NU; ++v) r[v] = (!W2V_ROW_GUARDS || lane + kWave * v < d) ? p[kWave * v] : 0.f;
-  }
-  if (W2V_ROW_BOUNDED) {
-    const uint32_t off = (uint32_t)(lane + kWave * (NV - 1)) * 4u;
-    const __amdgpu_buffer_rsrc_t rs = row_rsrc(M + row * pitch, d);
-    r[NV - 1] = __uint_as_float(fresh ? __builtin_amdgcn_raw_buffer_load_b32(rs, off, 0, kBufSc1)
-                                      : __builtin_amdgcn_raw_buffer_load_b32(rs, off, 0, 0));
+    for (int v = 0; v < NV; ++v) r[v] = p[kWave * v];
   }
 }
 
 template <int NV>
-__device__ __forceinline__ void store_row(float* M, int64_t row, int64_t pitch, int d, int lane,
-                                          const float (&r)[NV]) {
+__device__ __forceinline__ void store_row(float* M, int64_t row, int64_t pitch, int lane, const float (&r)[NV]) {
   float* p = M + row * pitch + lane;
-  constexpr int NU = W2V_ROW_BOUNDED ? NV - 1 : NV;
 #pragma unroll
-  for (int v = 0; v < NU; ++v)
-    if (!W2V_ROW_GUARDS || lane + kWave * v < d) p[kWave * v] = r[v];
-  if (W2V_ROW_BOUNDED)
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(r[NV - 1]), row_rsrc(M + row * pitch, d),
-                                          (uint32_t)(lane + kWave * (NV - 1)) * 4u, 0, 0);
+  for (int v = 0; v < NV; ++v) p[kWave * v] = r[v];
 }
 
 // row += delta, memory-side (no-return global_atomic_add_f32, 256 contiguous B
@@ -351,43 +305,29 @@ __device__ __forceinline__ void add_to_row(float* M, int64_t row, bool hot, int6
     atomic_add_row<NV>(M, row, pitch, d, lane, delta);
   } else {
     float cur[NV];
-    load_row<NV>(M, row, pitch, d, lane, false, cur);
+    load_row<NV>(M, row, pitch, lane, false, cur);
 #pragma unroll
     for (int v = 0; v < NV; ++v) cur[v] += delta[v];
-    if (!(W2V_EXP_SKIP & 64)) store_row<NV>(M, row, pitch, d, lane, cur);
+    store_row<NV>(M, row, pitch, lane, cur);
   }
 }
 
 // A privatised row's value is the global row plus this workgroup's pending delta.
 template <int NV>
 __device__ __forceinline__ void priv_read(const PrivRows& pr, int64_t row, int lane, float (&r)[NV]) {
-  if (W2V_EXP_SKIP & 256) return;
   const float* q = pr.delta + (row - pr.lo) * (NV * kWave) + lane;
 #pragma unroll
   for (int v = 0; v < NV; ++v) r[v] += q[kWave * v];
 }
 
 // Add delta into the row's pending delta, then mark the row dirty (after the
-// adds: a wave's LDS operations are ordered).
-//   W2V_PRIV_ADD 0 (rounds 1-4): ds_add_f32 per element. gfx950 runs an LDS float atomic
-//     one lane at a time: 192 cycles per wave instruction against 4 for
-//     ds_add_u32 and 10.5 for a ds_read + ds_write pair
-//     (tools/lds_atomic_bench.hip, profiles/r05d_lds_atomic_bench.log);
-//     on configs[1] these adds held ~44 % of the kernel's time (a build
-//     without them: 262 -> 468 M words/s, profiles/r05c_*).
-//   1: ds_read + v_add + ds_write, unguarded (timing experiments: two waves
-//     of a workgroup can lose an add, and a flush racing an add counts the
-//     row's delta twice).
-//   2 (the default): the same read-modify-write under a per-row LDS lock bit
-//     that lane 0 takes with one single-lane ds_or_rtn_b32 (a wave's own LDS
-//     operations execute in order, so the release after the writes publishes
-//     them); flush_private takes the same lock: exact, as the float atomics
-//     are. Same box, alternating (profiles/r05e_*): configs[1] 262 -> 330-337
-//     M words/s (unguarded 334-337), configs[0] / [2] unchanged, every
-//     headline-scale and full-concurrency quality gate passing.
-#ifndef W2V_PRIV_ADD  // 2 since round 5: configs[1] 262 -> 330-337 M words/s (profiles/r05e_2_ab_c2_lock.log)
-#define W2V_PRIV_ADD 2
-#endif
+// adds: a wave's LDS operations are ordered). The add is a ds_read + v_add +
+// ds_write under a per-row LDS lock bit that lane 0 takes with one single-lane
+// ds_or_rtn_b32 (a wave's own LDS operations execute in order, so the release
+// after the writes publishes them); flush_private takes the same lock, so no
+// add is lost or flushed twice. Not a float LDS atomic: gfx950 runs ds_add_f32
+// one lane at a time, 192 cycles per wave instruction against 10.5 for a
+// ds_read + ds_write pair (tools/lds_atomic_bench.hip).
 __device__ __forceinline__ void priv_lock(const PrivRows& pr, int p, int lane) {
   unsigned* w = pr.lock + (p >> 5);
   const unsigned bit = 1u << (p & 31);
@@ -405,28 +345,16 @@ __device__ __forceinline__ void priv_unlock(const PrivRows& pr, int p, int lane)
   if (lane == 0) atomicAnd(pr.lock + (p >> 5), ~(1u << (p & 31)));
 }
 template <int NV>
-__device__ __forceinline__ void priv_add(const PrivRows& pr, int64_t row, int d, int lane, const float (&delta)[NV]) {
+__device__ __forceinline__ void priv_add(const PrivRows& pr, int64_t row, int lane, const float (&delta)[NV]) {
   const int64_t p = row - pr.lo;
   float* q = pr.delta + p * (NV * kWave) + lane;
-  if (W2V_PRIV_ADD == 2) {
-    priv_lock(pr, (int)p, lane);
-    float cur[NV];
+  priv_lock(pr, (int)p, lane);
+  float cur[NV];
 #pragma unroll
-    for (int v = 0; v < NV; ++v) cur[v] = q[kWave * v];
+  for (int v = 0; v < NV; ++v) cur[v] = q[kWave * v];
 #pragma unroll
-    for (int v = 0; v < NV; ++v) q[kWave * v] = cur[v] + delta[v];  // padding: 0 + 0
-    priv_unlock(pr, (int)p, lane);
-  } else if (W2V_PRIV_ADD == 1) {
-    float cur[NV];
-#pragma unroll
-    for (int v = 0; v < NV; ++v) cur[v] = q[kWave * v];
-#pragma unroll
-    for (int v = 0; v < NV; ++v) q[kWave * v] = cur[v] + delta[v];  // padding: 0 + 0
-  } else {
-#pragma unroll
-    for (int v = 0; v < NV; ++v)
-      if (!(W2V_EXP_SKIP & 128) && (v < kFullVecs<NV> || lane + kWave * v < d)) atomicAdd(q + kWave * v, delta[v]);
-  }
+  for (int v = 0; v < NV; ++v) q[kWave * v] = cur[v] + delta[v];  // padding: 0 + 0
+  priv_unlock(pr, (int)p, lane);
   if (lane == 0) atomicOr(pr.dirty + (p >> 6), 1ull << (p & 63));
 }
 
@@ -437,53 +365,30 @@ __device__ __forceinline__ void priv_add(const PrivRows& pr, int64_t row, int d,
 // format has >= 2p + 2 bits, 53 >= 50; checked exhaustively for x in [1,
 // 2^30)), and HIP's f32 division is correctly rounded (no fast math): the same
 // bits as the f64 division at a fraction of its VALU cost.
-#ifndef W2V_NS_SIGMOID_F64  // timing experiments only: 1 = the f64 division (same bits, more VALU)
 __device__ __forceinline__ float ns_sigmoid(float e) { return 1.0f / (1.0f + e); }
-#else
-__device__ __forceinline__ float ns_sigmoid(float e) { return (float)(1.0 / (double)(1.0f + e)); }
-#endif
 
-// g of up to N targets at once (Word2Vec.cpp:240-242 HS, :263-264 NS): the
-// targets' dot products f[t] are wave-uniform, so target t's sigma and g are
-// evaluated in lane t — one exp / division sequence for the batch instead of
-// one per target (the same operations on the same values: bit-identical);
-// code_l holds target t's code (HS: the Huffman code; NS: 1 - label) in lane
-// c0 + t. Returns g in lane t (read back with readlane_f).
+// g of one target (Word2Vec.cpp:240-242 HS, :263-264 NS) from its dot product
+// fl and its code cl (HS: the Huffman code; NS: 1 - label). Each lane
+// evaluates a different target of the batch (batch_grad_l): one exp / division
+// sequence for the batch instead of one per target (the same operations on
+// the same values: bit-identical).
 template <bool HSF>
 __device__ __forceinline__ float grad_of(float fl, int cl, float alpha) {
   const float e = expf(-fl);
-#ifdef W2V_HS_F32  // timing experiments only: HS's sigma and g in f32 (not the reference's double)
-  if (HSF) return (1.0f - (float)cl - 1.0f / (1.0f + e)) * alpha;
-#endif
-  if (HSF) {
+  if (HSF) {  // the reference's double form (Word2Vec.cpp:240-242)
     const float s = (float)(1.0 / (1.0 + (double)e));
     return (float)((1.0 - (double)cl - (double)s) * (double)alpha);
   }
   return ((float)(1 - cl) - ns_sigmoid(e)) * alpha;
 }
 
-template <int N, bool HSF>
-__device__ __forceinline__ float batch_grad(const float (&f)[N], int T, int code_l, int c0, float alpha, int lane) {
-  float fl = 0.f;
-  int cl = 0;
-#pragma unroll
-  for (int t = 0; t < N; ++t) {
-    if (t < T) {
-      const int c = readlane_i(code_l, c0 + t);
-      fl = (lane == t) ? f[t] : fl;
-      cl = (lane == t) ? c : cl;
-    }
-  }
-  return grad_of<HSF>(fl, cl, alpha);
-}
-
 // ---------------------------------------------------------------------------
-// The dot products of a batch of targets, reduced together (W2V_BATCH_DOTS).
-// One wave_sum per target costs 6 DPP adds + a readlane each, and the batch's
-// sigma step then gathers the sums back into lanes (2 selects + a readlane per
-// target): ~13 VALU per target on a kernel that at d = 100 keeps the VALU busy
-// ~77 % of its cycles (profiles/r04c_c1_pmc_counters.json: SQ_ACTIVE_INST_VALU
-// / SQ_WAVE_CYCLES per SIMD). Instead the NB (4 or 8) per-lane partials are
+// The dot products of a batch of targets, reduced together. One wave_sum per
+// target would cost 6 DPP adds + a readlane each, and gathering the sums back
+// into lanes for the batch's sigma step 2 selects + a readlane per target:
+// ~13 VALU per target on a kernel that at d = 100 keeps the VALU busy ~77 % of
+// its cycles (profiles/r04c_c1_pmc_counters.json: SQ_ACTIVE_INST_VALU /
+// SQ_WAVE_CYCLES per SIMD). Instead the NB (4 or 8) per-lane partials are
 // folded pairwise, halving the vector count at each step:
 //   xor 32  v_permlane32_swap(a, b): a = [a.lo | b.lo], b = [a.hi | b.hi];
 //           a + b holds a's half-sums in lanes 0-31 and b's in lanes 32-63
@@ -495,9 +400,6 @@ __device__ __forceinline__ float batch_grad(const float (&f)[N], int T, int code
 // 18 VALU for 8 targets instead of ~104. The lanes of a group hold identical
 // bits (a + b == b + a). Only the order of the 64-term sum changes.
 // ---------------------------------------------------------------------------
-#ifndef W2V_BATCH_DOTS
-#define W2V_BATCH_DOTS 1
-#endif
 __device__ __forceinline__ void swap32(float& a, float& b) {
   const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
   a = __uint_as_float(r[0]);
@@ -556,8 +458,9 @@ __device__ __forceinline__ float batch_dots(const float (&p)[N], int lane) {
   return v;
 }
 
-// batch_grad over batch_dots' layout: lane L evaluates target batch_target(L)
-// (its code fetched with one permute); counts the batch's non-finite scores.
+// g of a batch in batch_dots' layout: lane L evaluates target batch_target(L)
+// (its code, held in lane c0 + t of code_l, fetched with one permute); counts
+// the batch's non-finite scores.
 template <int N, bool HSF>
 __device__ __forceinline__ float batch_grad_l(float fl, int T, int code_l, int c0, float alpha, int lane,
                                               unsigned long long* stats) {
@@ -622,7 +525,7 @@ __device__ __forceinline__ void apply_targets(float* M, int64_t pitch, int d, in
     rows[t] = readlane_i(row_l, t0 + t);
     priv[t] = pr.has(rows[t]);
     hot[t] = !priv[t] && rows[t] >= hot_lo && rows[t] < hot_hi;
-    if (t < T) load_row<NV>(M, rows[t], pitch, d, lane, hot[t] || priv[t], r[t]);
+    if (t < T) load_row<NV>(M, rows[t], pitch, lane, hot[t] || priv[t], r[t]);
   }
 #pragma unroll
   for (int t = 0; t < MAXT; ++t) {  // privatised rows: global value + this workgroup's pending delta
@@ -630,7 +533,6 @@ __device__ __forceinline__ void apply_targets(float* M, int64_t pitch, int d, in
       priv_read<NV>(pr, rows[t], lane, r[t]);
     }
   }
-#if W2V_BATCH_DOTS
   float pd[MAXT];
 #pragma unroll
   for (int t = 0; t < MAXT; ++t) {
@@ -643,53 +545,34 @@ __device__ __forceinline__ void apply_targets(float* M, int64_t pitch, int d, in
   }
   float g_l[kGroups<MAXT>];
   batch_g<MAXT, HSF>(pd, T, code_l, t0, alpha, lane, stats, g_l);
-#else
-  float f[MAXT];
-#pragma unroll
-  for (int t = 0; t < MAXT; ++t) {
-    f[t] = 0.f;
-    if (t < T) {
-      float p = 0.f;
-#pragma unroll
-      for (int v = 0; v < NV; ++v) p += r[t][v] * x[v];
-      f[t] = wave_sum(p);
-    }
-  }
-  const float g_l = batch_grad<MAXT, HSF>(f, T, code_l, t0, alpha, lane);
-#endif
 #pragma unroll
   for (int t = 0; t < MAXT; ++t) {
     if (t < T) {
-#if W2V_BATCH_DOTS
       const float gt = batch_gt<MAXT>(g_l, t);
-#else
-      if (stats) note_nonfinite(stats, !__builtin_isfinite(f[t]), lane);
-      const float gt = readlane_f(g_l, t);
-#endif
       float delta[NV];
 #pragma unroll
       for (int v = 0; v < NV; ++v) {
         g[v] += gt * r[t][v];  // grad uses the pre-update row (:244 / :266)
         delta[v] = gt * x[v];
       }
-      if (priv[t]) {  // ds_add_f32 into the workgroup's delta; flushed after the center
-        priv_add<NV>(pr, rows[t], d, lane, delta);
+      if (priv[t]) {  // into the workgroup's pending delta; flushed after the center
+        priv_add<NV>(pr, rows[t], lane, delta);
       } else if (hot[t]) {
-        if (!(W2V_EXP_SKIP & 1)) atomic_add_row<NV>(M, rows[t], pitch, d, lane, delta);
+        atomic_add_row<NV>(M, rows[t], pitch, d, lane, delta);
       } else {
 #pragma unroll
         for (int v = 0; v < NV; ++v) r[t][v] += delta[v];
-        if (!(W2V_EXP_SKIP & 64)) store_row<NV>(M, rows[t], pitch, d, lane, r[t]);
+        store_row<NV>(M, rows[t], pitch, lane, r[t]);
       }
     }
   }
 }
 
 // Move the workgroup's pending deltas of the dirty privatised rows into HBM
-// (memory-side float atomics). The dirty mask and every delta word are taken
-// with atomic swaps, so an add racing the flush from another wave of the
-// workgroup is neither lost nor flushed twice (its dirty bit is set after its
-// adds and survives until the next flush).
+// (memory-side float atomics). The dirty mask is taken with an atomic swap and
+// each row's delta under the row's lock, so an add racing the flush from
+// another wave of the workgroup is neither lost nor flushed twice (its dirty
+// bit is set after its adds and survives until the next flush).
 //
 // Scale: a row that n workgroups update within one flush interval receives
 // the mean of their deltas scaled to at most priv_avg concurrent
@@ -717,26 +600,17 @@ __device__ __forceinline__ void flush_private(const TrainArgs& a, const PrivRows
     const float sc = pr.ctx ? a.ctx_sc[p & (kCtxMax - 1)] : a.priv_sc[p];
     float* q = pr.delta + p * (NV * kWave) + lane;
     float* dst = pr.M + (pr.lo + p) * a.pitch + lane;
-    if (W2V_PRIV_ADD == 2) {  // take the row under its lock (priv_add)
-      float val[NV];
-      priv_lock(pr, p, lane);
+    float val[NV];
+    priv_lock(pr, p, lane);  // take the row under its lock (priv_add)
 #pragma unroll
-      for (int v = 0; v < NV; ++v) val[v] = q[kWave * v];
+    for (int v = 0; v < NV; ++v) val[v] = q[kWave * v];
 #pragma unroll
-      for (int v = 0; v < NV; ++v) q[kWave * v] = 0.0f;
-      priv_unlock(pr, p, lane);
+    for (int v = 0; v < NV; ++v) q[kWave * v] = 0.0f;
+    priv_unlock(pr, p, lane);
 #pragma unroll
-      for (int v = 0; v < NV; ++v)
-        if (val[v] != 0.0f && !(W2V_EXP_SKIP & 2))  // 0 past word_dim: skipped
-          (void)__hip_atomic_fetch_add(dst + kWave * v, val[v] * sc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      continue;
-    }
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-      const float val = atomicExch(q + kWave * v, 0.0f);  // 0 past word_dim: skipped
-      if (val != 0.0f && !(W2V_EXP_SKIP & 2))
-        (void)__hip_atomic_fetch_add(dst + kWave * v, val * sc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    for (int v = 0; v < NV; ++v)
+      if (val[v] != 0.0f)  // 0 past word_dim: skipped
+        (void)__hip_atomic_fetch_add(dst + kWave * v, val[v] * sc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
@@ -755,7 +629,7 @@ __device__ __forceinline__ void hs_gather(const TrainArgs& a, int T, int row_l, 
   for (int t = 0; t < MT; ++t) {
     if (t < T) {
       const int row = readlane_i(row_l, t0 + t);
-      load_row<NV>(a.S, row, a.pitch, a.dim, lane, pr.has(row) || row >= a.hot_s, r[t]);
+      load_row<NV>(a.S, row, a.pitch, lane, pr.has(row) || row >= a.hot_s, r[t]);
     }
   }
 }
@@ -772,7 +646,6 @@ __device__ __forceinline__ void hs_score(const TrainArgs& a, int T, int row_l, i
       const int row = readlane_i(row_l, t0 + t);
       if (pr.has(row)) priv_read<NV>(pr, row, lane, r[t]);
     }
-#if W2V_BATCH_DOTS
   float pd[MT];
 #pragma unroll
   for (int t = 0; t < MT; ++t) {
@@ -785,30 +658,11 @@ __device__ __forceinline__ void hs_score(const TrainArgs& a, int T, int row_l, i
   }
   float g_l[kGroups<MT>];
   batch_g<MT, true>(pd, T, code_l, t0, alpha, lane, a.stats, g_l);
-#else
-  float f[MT];
-#pragma unroll
-  for (int t = 0; t < MT; ++t) {
-    f[t] = 0.f;
-    if (t < T) {
-      float p = 0.f;
-#pragma unroll
-      for (int v = 0; v < NV; ++v) p += r[t][v] * x[v];
-      f[t] = wave_sum(p);
-    }
-  }
-  const float g_l = batch_grad<MT, true>(f, T, code_l, t0, alpha, lane);
-#endif
 #pragma unroll
   for (int t = 0; t < MT; ++t) {
     gt[t] = 0.f;
     if (t < T) {
-#if W2V_BATCH_DOTS
       gt[t] = batch_gt<MT>(g_l, t);
-#else
-      note_nonfinite(a.stats, !__builtin_isfinite(f[t]), lane);
-      gt[t] = readlane_f(g_l, t);
-#endif
 #pragma unroll
       for (int v = 0; v < NV; ++v) g[v] += gt[t] * r[t][v];
     }
@@ -828,18 +682,18 @@ __device__ __forceinline__ void hs_apply(const TrainArgs& a, int T, int row_l, i
 #pragma unroll
       for (int v = 0; v < NV; ++v) delta[v] = gt[t] * x[v];
       if (pr.has(row)) {
-        priv_add<NV>(pr, row, a.dim, lane, delta);
+        priv_add<NV>(pr, row, lane, delta);
       } else if (row >= a.hot_s) {
         if (a.hot_sc) {  // damped to the hot-node average (wave-uniform row: one scalar load)
           const float s = a.hot_sc[row - a.hot_s];
 #pragma unroll
           for (int v = 0; v < NV; ++v) delta[v] *= s;
         }
-        if (!(W2V_EXP_SKIP & 1)) atomic_add_row<NV>(a.S, row, a.pitch, a.dim, lane, delta);
+        atomic_add_row<NV>(a.S, row, a.pitch, a.dim, lane, delta);
       } else {
 #pragma unroll
         for (int v = 0; v < NV; ++v) r[t][v] += delta[v];
-        if (!(W2V_EXP_SKIP & 64)) store_row<NV>(a.S, row, a.pitch, a.dim, lane, r[t]);
+        store_row<NV>(a.S, row, a.pitch, lane, r[t]);
       }
     }
   }
@@ -848,11 +702,7 @@ __device__ __forceinline__ void hs_apply(const TrainArgs& a, int T, int row_l, i
 template <int NV, int MAXT>
 __device__ __forceinline__ void hs_word(const TrainArgs& a, int word, int lane, const float (&x)[NV],
                                         float (&g)[NV], float alpha, Counters& cnt, float* lds) {
-#ifndef W2V_HS_MT
   constexpr int MT = MAXT / 2 > 0 ? MAXT / 2 : 1;  // two buffers of MT rows: the same registers as one of MAXT
-#else  // experiments (tools/r03): rows per pipelined batch
-  constexpr int MT = W2V_HS_MT;
-#endif
   const PrivRows pr = (a.priv_M == a.S) ? out_rows<NV>(a, lds) : PrivRows();
   const int64_t cb = a.coff[word];
   const int L = (int)(a.coff[word + 1] - cb);
@@ -913,109 +763,6 @@ __device__ __forceinline__ void apply_list(const TrainArgs& a, float* M, int T, 
   cnt.targets += (unsigned long long)T;
 }
 
-// Two consecutive contexts' NS updates as one batch (skip-gram, negative <=
-// kPairNeg): context A's targets in slots [0, T1), context B's in [kPairHalf,
-// kPairHalf + T2). All rows are gathered at once, so B's gathers no longer
-// wait behind A's stores and memory-side atomics (vmcnt retires in order).
-// The reference applies A before B (Word2Vec.cpp:329-349): a B target that
-// is also one of A's takes A's updated row from the registers — the same fp32
-// `row + g * x` a re-read would return on the sequential schedule, so parity
-// is unchanged — and A's gradient terms accumulate before B's.
-constexpr int kPairHalf = 6;
-constexpr int kPairNeg = kPairHalf - 1;
-#ifndef W2V_NS_PAIR  // 1: two contexts per batch (measured: no gain; off)
-#define W2V_NS_PAIR 0
-#endif
-#ifndef W2V_NS_PAIR_MIN_NV
-#define W2V_NS_PAIR_MIN_NV 3
-#endif
-template <int NV>
-constexpr bool kNsPair = W2V_NS_PAIR && NV >= W2V_NS_PAIR_MIN_NV;  // d <= 128 keeps 64 VGPRs (8 waves/SIMD)
-
-template <int NV>
-__device__ __forceinline__ void pair_update(float* M, int64_t pitch, int d, int lane, int row, bool hot, bool priv,
-                                            int code, float f, const float (&x)[NV], float (&g)[NV], float alpha,
-                                            float (&r)[NV], const PrivRows& pr, unsigned long long* stats) {
-  note_nonfinite(stats, !__builtin_isfinite(f), lane);
-  const float e = expf(-f);
-  const float s = ns_sigmoid(e);
-  const float gt = ((float)(1 - code) - s) * alpha;
-  float delta[NV];
-#pragma unroll
-  for (int v = 0; v < NV; ++v) {
-    g[v] += gt * r[v];  // grad uses the pre-update row (:266)
-    delta[v] = gt * x[v];
-    r[v] += delta[v];   // the updated row, for a later target of the other context
-  }
-  if (priv) {
-    priv_add<NV>(pr, row, d, lane, delta);
-  } else if (hot) {
-    if (!(W2V_EXP_SKIP & 1)) atomic_add_row<NV>(M, row, pitch, d, lane, delta);
-  } else {
-    store_row<NV>(M, row, pitch, d, lane, r);
-  }
-}
-
-template <int NV>
-__device__ __forceinline__ void apply_pair(const TrainArgs& a, float* M, int T1, int T2, int row_l, int lane,
-                                           const float (&x)[NV], float (&g)[NV], float alpha, const PrivRows& pr) {
-  constexpr int H = kPairHalf, MP = 2 * kPairHalf;
-  float r[MP][NV];
-  int rows[MP];
-  bool hot[MP], priv[MP], use[MP];
-#pragma unroll
-  for (int t = 0; t < MP; ++t) {
-    use[t] = t < H ? t < T1 : t - H < T2;
-    rows[t] = readlane_i(row_l, t);
-    priv[t] = pr.has(rows[t]);
-    hot[t] = !priv[t] && rows[t] < a.hot_wc;
-    if (use[t]) load_row<NV>(M, rows[t], a.pitch, a.dim, lane, hot[t] || priv[t], r[t]);
-  }
-#pragma unroll
-  for (int t = 0; t < MP; ++t)
-    if (use[t] && priv[t]) priv_read<NV>(pr, rows[t], lane, r[t]);
-  // context A: every score from the gathered rows, then the updates in target order
-  float f[MP];
-#pragma unroll
-  for (int t = 0; t < H; ++t) {
-    f[t] = 0.f;
-    if (use[t]) {
-      float p = 0.f;
-#pragma unroll
-      for (int v = 0; v < NV; ++v) p += r[t][v] * x[v];
-      f[t] = wave_sum(p);
-    }
-  }
-#pragma unroll
-  for (int t = 0; t < H; ++t)
-    if (use[t]) pair_update<NV>(M, a.pitch, a.dim, lane, rows[t], hot[t], priv[t], t == 0 ? 0 : 1, f[t], x, g, alpha,
-                                r[t], pr, a.stats);
-  // context B: a row A updated continues from A's result (targets of one
-  // context are distinct, so at most one A slot matches)
-#pragma unroll
-  for (int t = H; t < MP; ++t)
-#pragma unroll
-    for (int u = 0; u < H; ++u)
-      if (use[t] && use[u] && rows[t] == rows[u]) {
-#pragma unroll
-        for (int v = 0; v < NV; ++v) r[t][v] = r[u][v];
-      }
-#pragma unroll
-  for (int t = H; t < MP; ++t) {
-    f[t] = 0.f;
-    if (use[t]) {
-      float p = 0.f;
-#pragma unroll
-      for (int v = 0; v < NV; ++v) p += r[t][v] * x[v];
-      f[t] = wave_sum(p);
-    }
-  }
-#pragma unroll
-  for (int t = H; t < MP; ++t)
-    if (use[t]) pair_update<NV>(M, a.pitch, a.dim, lane, rows[t], hot[t], priv[t], t == H ? 0 : 1, f[t], x, g, alpha,
-                                r[t], pr, a.stats);
-}
-
 // NS with positive `word` against `negw_l` lanes [base, base + neg).
 template <int NV, int MAXT>
 __device__ __forceinline__ void ns_word(const TrainArgs& a, float* M, int word, int negw_l, int base, int lane,
@@ -1038,9 +785,6 @@ __device__ __forceinline__ void ns_word(const TrainArgs& a, float* M, int word, 
 // targets are applied before the next chunk's are found (a duplicate test
 // needs only the words, not the rows).
 // ---------------------------------------------------------------------------
-#ifndef W2V_MANY_NEG  // timing experiments only: 0 compiles the path out (negative >= 64 then trains wrongly)
-#define W2V_MANY_NEG 1
-#endif
 template <bool REPLAY>
 __device__ __forceinline__ int draw_chunk(const TrainArgs& a, uint32_t s, uint32_t i, int slot, int ch, int lane,
                                           const uint32_t* rp) {
@@ -1118,7 +862,7 @@ __device__ __forceinline__ void sg_center(const TrainArgs& a, float* lds, const 
   const bool hot_c = c < a.hot_wc;
   float x[NV], g[NV];
   if (a.strict) drain_vmem();
-  load_row<NV>(a.W, c, a.pitch, a.dim, lane, hot_c, x);
+  load_row<NV>(a.W, c, a.pitch, lane, hot_c, x);
 #pragma unroll
   for (int v = 0; v < NV; ++v) g[v] = 0.f;
   const int ctx_l = (lane < span) ? sent[lo + lane] : 0;
@@ -1126,37 +870,6 @@ __device__ __forceinline__ void sg_center(const TrainArgs& a, float* lds, const 
   cnt.contexts += (unsigned long long)(span - 1);
   const int nctx = span - 1;
   const int neg = a.negative;
-  if (NS && !HS && kNsPair<NV> && neg <= kPairNeg && span <= kWave) {
-    // contexts two at a time (apply_pair); the table draws of G2 contexts at once
-    const int me = i - lo;
-    const int cw_l = sent[lo + min(lane + (lane >= me ? 1 : 0), span - 1)];  // lane k: the k-th context word
-    const int G2 = max(2, (kWave / neg) & ~1);
-    const PrivRows pr = (a.priv_M == a.C) ? out_rows<NV>(a, lds) : PrivRows();
-    int negw_l = 0;
-    for (int k = 0; k < nctx; k += 2) {
-      const int gs = k % G2;
-      if (gs == 0) {
-        const int nd = min(G2, nctx - k) * neg;
-        negw_l = draw_negatives<REPLAY>(a, s, (uint32_t)i, k, nd, lane, rp);
-        cnt.draws += (unsigned long long)nd;
-      }
-      int ta = 0, tb = 0;
-      const int T1 = ns_targets(neg, readlane_i(cw_l, k), negw_l, gs * neg, lane, ta);
-      const int T2 = (k + 1 < nctx) ? ns_targets(neg, readlane_i(cw_l, k + 1), negw_l, (gs + 1) * neg, lane, tb) : 0;
-      // every lane takes part in the permute: a lane whose exec bit is off
-      // supplies no data to ds_bpermute, so a shuffle under `lane >= kPairHalf`
-      // would read B's targets from switched-off lanes 0..5
-      const int tb_s = __shfl(tb, (lane - kPairHalf) & (kWave - 1));
-      const int tgt_l = lane < kPairHalf ? ta : tb_s;
-      if (a.strict) drain_vmem();
-      apply_pair<NV>(a, a.C, T1, T2, tgt_l, lane, x, g, alpha, pr);
-      cnt.targets += (unsigned long long)(T1 + T2);
-    }
-    cnt.stamp(3);
-    add_to_row<NV>(a.W, c, hot_c, a.pitch, a.dim, lane, g);  // W.row(center) += neu1_grad (:351)
-    cnt.stamp(4);
-    return;
-  }
   const int G = NS ? max(1, kWave / max(neg, 1)) : 1;
   int negw_l = 0;
   int slot = 0;
@@ -1164,7 +877,7 @@ __device__ __forceinline__ void sg_center(const TrainArgs& a, float* lds, const 
     if (j == i) continue;
     const int w = (j - lo < kWave) ? readlane_i(ctx_l, j - lo) : uniform_i(sent[j]);  // window > 31: span > 64
     if (HS) hs_word<NV, MAXT>(a, w, lane, x, g, alpha, cnt, lds);
-    if (W2V_MANY_NEG && NS && neg >= kWave) {
+    if (NS && neg >= kWave) {
       ns_word_many<NV, MAXT, REPLAY>(a, a.C, w, s, (uint32_t)i, slot, lane, x, g, alpha, cnt, lds, rp);
     } else if (NS) {
       const int gs = slot % G;
@@ -1202,7 +915,7 @@ __device__ __forceinline__ void cbow_tail(const TrainArgs& a, float* lds, int i,
     for (int t = 0; t < MAXT; ++t)
       if (r0 + t < U) {
         const int row = row_of(r0 + t);
-        load_row<NV>(a.C, row, a.pitch, a.dim, lane, row < a.hot_wc || cx.has(row), rr[t]);
+        load_row<NV>(a.C, row, a.pitch, lane, row < a.hot_wc || cx.has(row), rr[t]);
       }
 #pragma unroll
     for (int t = 0; t < MAXT; ++t)
@@ -1220,7 +933,7 @@ __device__ __forceinline__ void cbow_tail(const TrainArgs& a, float* lds, int i,
   }
   cnt.stamp(2);
   if (HS) hs_word<NV, MAXT>(a, c, lane, h, g, alpha, cnt, lds);
-  if (W2V_MANY_NEG && NS && a.negative >= kWave) {
+  if (NS && a.negative >= kWave) {
     ns_word_many<NV, MAXT, REPLAY>(a, a.W, c, s, (uint32_t)i, 0, lane, h, g, alpha, cnt, lds, rp);
   } else if (NS) {
     const int nd = a.negative;
@@ -1243,20 +956,20 @@ __device__ __forceinline__ void cbow_tail(const TrainArgs& a, float* lds, int i,
     for (int t = 0; t < MAXT; ++t)
       if (r0 + t < U) {
         const int row = row_of(r0 + t);
-        if (!cx.has(row) && row >= a.hot_wc) load_row<NV>(a.C, row, a.pitch, a.dim, lane, false, cur[t]);
+        if (!cx.has(row) && row >= a.hot_wc) load_row<NV>(a.C, row, a.pitch, lane, false, cur[t]);
       }
 #pragma unroll
     for (int t = 0; t < MAXT; ++t)
       if (r0 + t < U) {
         const int row = row_of(r0 + t);
         if (cx.has(row)) {
-          priv_add<NV>(cx, row, a.dim, lane, g);
+          priv_add<NV>(cx, row, lane, g);
         } else if (row < a.hot_wc) {
-          if (!(W2V_EXP_SKIP & 4)) atomic_add_row<NV>(a.C, row, a.pitch, a.dim, lane, g);
+          atomic_add_row<NV>(a.C, row, a.pitch, a.dim, lane, g);
         } else {
 #pragma unroll
           for (int v = 0; v < NV; ++v) cur[t][v] += g[v];
-          if (!(W2V_EXP_SKIP & 64)) store_row<NV>(a.C, row, a.pitch, a.dim, lane, cur[t]);
+          store_row<NV>(a.C, row, a.pitch, lane, cur[t]);
         }
       }
   }
@@ -1379,10 +1092,8 @@ __device__ __forceinline__ void cbow_center_wide(const TrainArgs& a, float* lds,
                                       rp, cnt, lane);
 }
 
-// Any window past kMaxWideWindow (the reference takes any, Word2Vec.cpp:285): cbow_center_huge.
-constexpr int kMaxWindow = (1 << 20) - 1;
-
-// CBOW center for windows past kMaxWideWindow: the same set semantics and
+// CBOW center for windows past kMaxWideWindow (the reference takes any window,
+// Word2Vec.cpp:285): the same set semantics and
 // ascending visiting order as cbow_center, with the span read from the
 // sentence 64 positions at a time. Pass 1 marks each position that is not a
 // repeat of an earlier valid one (a scalar walk over the earlier positions)
@@ -1470,7 +1181,7 @@ __device__ __forceinline__ void center(const TrainArgs& a, float* lds, const int
     // center count, and the wave that completes every flush_every-th center
     // drains the deltas all of them accumulated (one atomic per dirty row
     // instead of one per update and wave).
-    unsigned* done = reinterpret_cast<unsigned*>(lds) + 8;
+    unsigned* done = reinterpret_cast<unsigned*>(lds) + kLdsCenters;
     unsigned n = 0;
     if (lane == 0) n = atomicAdd(done, 1u) + 1u;
     n = (unsigned)__builtin_amdgcn_readfirstlane((int)n);
@@ -1491,7 +1202,7 @@ __device__ __forceinline__ void train_epoch(const TrainArgs& a) {
   const int lane = lane_id();
   float* lds = (a.priv_n + a.ctx_n) > 0 ? w2v_lds : nullptr;
   if (lds) {
-    const int64_t words = lds_header_words(a.priv_n, a.ctx_n) + (int64_t)(a.priv_n + a.ctx_n) * (NV * kWave);
+    const int64_t words = kLdsHeaderWords + (int64_t)(a.priv_n + a.ctx_n) * (NV * kWave);
     for (int64_t k = threadIdx.x; k < words; k += blockDim.x) lds[k] = 0.0f;
     __syncthreads();
   }

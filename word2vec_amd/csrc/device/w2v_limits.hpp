@@ -21,27 +21,25 @@ template <int NV>
 constexpr int kMaxBlock = max_block(NV);
 // Waves per SIMD the epoch kernel is compiled for: two 16-wave workgroups per
 // CU when a row is <= 2 floats per lane (d <= 128: 64 VGPRs), else one.
-#ifndef W2V_MIN_WAVES
 constexpr int min_waves(int nv) { return nv <= 2 ? 8 : nv <= 16 ? 4 : 2; }  // d > 1024: 256 VGPRs
-#else  // occupancy experiments (tools/r02/occ_probe.sh)
-constexpr int min_waves(int) { return W2V_MIN_WAVES; }
-#endif
 template <int NV>
 constexpr int kMinWaves = min_waves(NV);
 
 // LDS the shared-negatives kernel gives its row slots (w2v_shared.hpp kSnPriv; <= 32 rows):
 // 20 KiB = 10 rows at d = 512 with four 2-wave workgroups per CU (38.9 KiB each).
-#ifndef W2V_SN_PRIV_BYTES
 constexpr int kSnPrivBytes = 20 * 1024;
-#else  // experiments (tools/r02/sn_slots_probe.sh)
-constexpr int kSnPrivBytes = W2V_SN_PRIV_BYTES;
-#endif
 
 // LDS-privatised rows of the per-pair kernel (layout: w2v_kernels.hpp): the
 // output range holds at most kPrivMax rows, the context range kCtxMax.
 constexpr int kPrivMax = 128;
 constexpr int kCtxMax = 64;
-W2V_HD inline int64_t lds_header_words(int64_t, int64_t) { return 16; }
+// The region's header, in 32-bit words, then the pending deltas.
+constexpr int kLdsDirtyOut = 0;   // [0, 4): dirty mask of the output rows (2 x 64 bits)
+constexpr int kLdsDirtyCtx = 4;   // [4, 8): dirty mask of the context rows
+constexpr int kLdsCenters = 8;    // centers of the workgroup
+constexpr int kLdsLockOut = 9;    // [9, 13): lock bits of the output rows
+constexpr int kLdsLockCtx = 13;   // [13, 15): lock bits of the context rows
+constexpr int kLdsHeaderWords = 16;
 
 constexpr int kWideChunks = 4;  // wide-window CBOW kernels: window <= 32 * kWideChunks - 1 in registers
 constexpr int kMaxWideWindow = 32 * kWideChunks - 1;

@@ -380,7 +380,7 @@ constexpr double kSnPressure = 0.06;
 // Round 2 set 128 flushes per workgroup and a 256 cap (configs[1] 152 -> 173
 // M words/s; the planted corpus lost 3-5 similarity points when forced to
 // 256). Round 5, with the private rows' LDS adds no longer the bottleneck
-// (W2V_PRIV_ADD), the flush atomics and the rows' write traffic are: configs[1]
+// (priv_add's per-row lock), the flush atomics and the rows' write traffic are: configs[1]
 // at 256 / 128 / 512 / 1024 node-interval (context at half) runs 331-341 /
 // 426 / 443 M words/s (profiles/r05i_1_*, r05j_1_ab_c2_flush.log), its
 // headline-scale paired gate +13.3 / +6.3, +16.4 / +6.3, +13.5 / +2.5
@@ -429,7 +429,7 @@ void hot_node_scales(const PolicyInput& in, LaunchPlan& p, double waves, int64_t
 // and, for CBOW, of the hottest context rows of C (contexts are not
 // subsampled: the most frequent words sit in most windows): as many rows as
 // fit 10 KiB per wave of the workgroup, <= kPrivMax per range (the dirty masks),
-// the output rows first. Layout: lds_header_words in w2v_limits.hpp. Parallel
+// the output rows first. Layout: kLdsHeaderWords in w2v_limits.hpp. Parallel
 // schedule only: the reference-exact schedule keeps per-update rounding.
 void plan_private_rows(const PolicyInput& in, LaunchPlan& p, int wpb, bool plain_cache) {
   const Knobs& kn = in.knobs;
@@ -437,11 +437,11 @@ void plan_private_rows(const PolicyInput& in, LaunchPlan& p, int wpb, bool plain
   const int64_t row_bytes = (int64_t)in.nv * kWave * (int64_t)sizeof(float);
   int64_t per_wave = 10 * 1024;
   if (kn.lds_per_wave > 0) per_wave = kn.lds_per_wave;  // experiments
-  int64_t budget = std::min<int64_t>(160 * 1024, per_wave * (int64_t)wpb) - 4 * lds_header_words(kPrivMax, 64);
+  int64_t budget = std::min<int64_t>(160 * 1024, per_wave * (int64_t)wpb) - 4 * kLdsHeaderWords;
   if (plain_cache) {
     const int64_t n_cu = in.n_cu > 0 ? in.n_cu : 1;
     const int64_t wg_per_cu = std::max<int64_t>(1, ((max_waves + n_cu - 1) / n_cu + wpb - 1) / wpb);
-    budget = 160 * 1024 / wg_per_cu - 4 * lds_header_words(kPrivMax, 64);
+    budget = 160 * 1024 / wg_per_cu - 4 * kLdsHeaderWords;
   }
   int64_t fit = budget / row_bytes;
   // <= 64 output rows by default for CBOW and HS. Skip-gram NS takes
@@ -509,7 +509,7 @@ void plan_private_rows(const PolicyInput& in, LaunchPlan& p, int wpb, bool plain
   else if (plain_hs) Q = 0;
   else if (rate > 0.0) Q = std::min(Q, by_rate.second);
   if (Q > 0) p.ctx_n = (int32_t)Q;
-  if (P + Q > 0) p.lds_bytes = lds_header_words(P, Q) * (int64_t)sizeof(float) + (P + Q) * row_bytes;
+  if (P + Q > 0) p.lds_bytes = kLdsHeaderWords * (int64_t)sizeof(float) + (P + Q) * row_bytes;
 }
 
 // Sentence segments as work items (parallel Philox schedule): the launch's
