@@ -6,10 +6,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <utility>
 #include <vector>
@@ -49,19 +49,6 @@ int fail(int code, const std::string& msg) {
   return code;
 }
 
-#define HIP_TRY(expr)                                                                \
-  do {                                                                               \
-    hipError_t e_ = (expr);                                                          \
-    if (e_ != hipSuccess)                                                            \
-      return fail(W2V_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
-  } while (0)
-
-template <class T>
-void dfree(T*& p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
-
 }  // namespace
 
 using w2v::Knobs;  // the experiment knobs (w2v_policy.hpp)
@@ -93,13 +80,12 @@ static Knobs read_knobs() {
 
 // A resident corpus (token ids + sentence offsets). Handles on one device may
 // train on one copy (w2v_dev_share_corpus: replicas of configs[3]'s 40 GB of
-// ids); each holds a reference and the last one to let go frees it, so an
-// owner that is destroyed or re-uploads its corpus never frees buffers a
-// borrower's kernels still read.
+// ids); each holds it through a shared_ptr and the last one to let go frees
+// it, so an owner that is destroyed or re-uploads its corpus never frees
+// buffers a borrower's kernels still read.
 struct CorpusBuf {
-  int32_t* ids = nullptr;
-  int64_t* soff = nullptr;
-  std::atomic<int> refs{1};  // handles on different host threads may share one corpus
+  w2v::DevBuf<int32_t> ids;
+  w2v::DevBuf<int64_t> soff;
 };
 
 struct w2v_dev {
@@ -114,34 +100,32 @@ struct w2v_dev {
   int nv = 1;                 // floats per lane per row (instantiated width >= ceil(d / 64))
   w2v::PolicySettings set;   // the update policy's setters (w2v_dev_set_hot_rows ... w2v_dev_set_private_rate)
   bool need_C = false, need_S = false;
+  // The model the kernels read, and its memory when the handle allocated it:
+  // the buffers stay empty when w2v_dev_bind_model supplied the caller's.
   float* W = nullptr;
   float* C = nullptr;
   float* S = nullptr;
-  float* keep = nullptr;
-  uint32_t* table = nullptr;
-  uint8_t* codes = nullptr;
-  int32_t* points = nullptr;
-  int64_t* coff = nullptr;
+  w2v::DevBuf<float> W_own, C_own, S_own;
+  w2v::DevBuf<float> keep;
+  w2v::DevBuf<uint32_t> table;
+  w2v::DevBuf<uint8_t> codes;
+  w2v::DevBuf<int32_t> points;
+  w2v::DevBuf<int64_t> coff;
   int64_t n_codes = 0;
-  int32_t* ids = nullptr;
-  int64_t* soff = nullptr;
-  CorpusBuf* corpus = nullptr;     // owns ids / soff, shared with the handles training on it
+  std::shared_ptr<CorpusBuf> corpus;  // shared with the handles training on it
   int64_t n_tok = 0, n_sent = 0, train_words = 0;
   int64_t max_len = 0;        // longest sentence (tokens)
-  int64_t* order = nullptr;
+  w2v::DevBuf<int64_t> order;
   int64_t n_order = 0;        // entries of `order` set by w2v_dev_set_order
-  uint32_t* replay = nullptr;
-  int64_t* replay_off = nullptr;
+  w2v::DevBuf<uint32_t> replay;
+  w2v::DevBuf<int64_t> replay_off;
   int64_t n_replay_off = 0;
-  unsigned long long* counters = nullptr;  // [0] words, [1..5] stats
-  unsigned int* work = nullptr;
-  float* scratch_f = nullptr;      // x | grad | rows for apply_rows
-  uint8_t* scratch_codes = nullptr;
-  int64_t scratch_n = 0;           // floats in scratch_f
-  int32_t* wide_scratch = nullptr; // CBOW windows past kMaxWideWindow: per-wave id slices (cbow_center_huge)
-  int64_t wide_scratch_n = 0;      // ints in wide_scratch
-  float* xfer_f = nullptr;         // row-sparse transfers: packed rows | row ids
-  int64_t xfer_n = 0;
+  w2v::DevBuf<unsigned long long> counters;  // [0] words, [1..5] stats
+  w2v::DevBuf<unsigned int> work;
+  w2v::DevBuf<float> scratch_f;      // x | grad | rows for apply_rows
+  w2v::DevBuf<uint8_t> scratch_codes;
+  w2v::DevBuf<int32_t> wide_scratch; // CBOW windows past kMaxWideWindow: per-wave id slices (cbow_center_huge)
+  w2v::DevBuf<float> xfer_f;         // row-sparse transfers: packed rows | row ids
   float fixed_alpha = 0.0f;
   int32_t rng = W2V_RNG_PHILOX;
   uint64_t seed = 0;
@@ -149,7 +133,6 @@ struct w2v_dev {
   int32_t update = W2V_UPDATE_PER_PAIR;
   int n_cu = 256;
   bool model_ready = false, vocab_ready = false, corpus_ready = false;
-  bool model_bound = false;  // W/C/S owned by the caller
   // Host copies of the vocab and corpus uploads, for the update policy's
   // frequency-derived settings (stats_of: flush scales, automatic hot rows):
   std::vector<float> keep_h;        // sample probabilities
@@ -163,8 +146,18 @@ struct w2v_dev {
   w2v::LaunchPlan last_plan;        // what the last launch's policy decided (w2v_dev_launch_plan)
   // the device copy of last_plan.hot_sc and the scales it holds
   std::vector<float> hot_sc_h;
-  float* hot_sc_d = nullptr;
-  int64_t hot_sc_cap = 0;
+  w2v::DevBuf<float> hot_sc_d;
+
+  ~w2v_dev() {  // the buffers free themselves after this
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+    if (own_stream && stream) (void)hipStreamDestroy(stream);
+  }
+  // Let go of the handle's own model memory (W / C / S then view nothing).
+  void drop_model() {
+    W_own.reset(), C_own.reset(), S_own.reset();
+    W = C = S = nullptr;
+  }
 };
 
 namespace w2v {
@@ -240,23 +233,42 @@ KernelFn kernel_deep_for(const w2v_dev* h) { return kernels_for_need(h->nv).pick
 w2v::ApplyFn apply_for(const w2v_dev* h) { return kernels_for_need(h->nv).pick_apply(); }
 
 int set_device(w2v_dev* h) {
-  HIP_TRY(hipSetDevice(h->device));
+  W2V_HIP_TRY(hipSetDevice(h->device));
   return W2V_OK;
 }
 
-// Drop the handle's reference to its corpus; the buffers are freed with the
-// last reference (w2v_dev_share_corpus).
-void release_corpus(w2v_dev* h) {
-  if (h->corpus && --h->corpus->refs == 0) {
-    dfree(h->corpus->ids);
-    dfree(h->corpus->soff);
-    delete h->corpus;
-  }
-  h->corpus = nullptr;
-  h->ids = nullptr;
-  h->soff = nullptr;
-  dfree(h->order);
-  h->corpus_ready = false;
+// Make `c` the handle's corpus (the three entrances: upload, adopt, share).
+// The handle lets go of its old one here, after the last step that can fail;
+// the last handle to let go of a corpus frees it.
+int install_corpus(w2v_dev* h, std::shared_ptr<CorpusBuf> c, int64_t n_tok, int64_t n_sent, int64_t max_len,
+                   int64_t train_words, std::vector<int64_t> hist) {
+  w2v::DevBuf<int64_t> order;
+  if (int rc = order.alloc((size_t)(n_sent > 0 ? n_sent : 1))) return rc;
+  h->corpus = std::move(c);
+  h->order = std::move(order);
+  h->n_tok = n_tok;
+  h->n_sent = n_sent;
+  h->n_order = 0;
+  h->max_len = max_len;
+  h->train_words = train_words;
+  h->tok_count = std::move(hist);  // also the flush-scale statistics (priv_scales)
+  ++h->data_version;
+  h->corpus_ready = true;
+  return W2V_OK;
+}
+
+// h->stream, the counters and the device's size, for w2v_dev_create.
+int init_device(w2v_dev* h) {
+  W2V_HIP_TRY(hipSetDevice(h->device));
+  W2V_HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  h->own_stream = true;
+  if (int rc = h->counters.alloc(8)) return rc;
+  W2V_HIP_TRY(hipMemset(h->counters.get(), 0, 8 * sizeof(unsigned long long)));
+  if (int rc = h->work.alloc(1)) return rc;
+  int ncu = 0;
+  W2V_HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->device));
+  h->n_cu = ncu > 0 ? ncu : 256;
+  return W2V_OK;
 }
 
 }  // namespace
@@ -323,20 +335,10 @@ int w2v_dev_create(const w2v_dev_config* cfg, w2v_dev** out) {
       return fail(W2V_ERR_HIP, std::string("hipGetDevice: ") + hipGetErrorString(e));
     }
   }
-  hipError_t e = hipSetDevice(h->device);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipMalloc(&h->counters, 8 * sizeof(unsigned long long));
-  if (e == hipSuccess) e = hipMemset(h->counters, 0, 8 * sizeof(unsigned long long));
-  if (e == hipSuccess) e = hipMalloc(&h->work, sizeof(unsigned int));
-  int ncu = 0;
-  if (e == hipSuccess) e = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->device);
-  if (e != hipSuccess) {
-    std::string msg = std::string("w2v_dev_create: ") + hipGetErrorString(e);
-    w2v_dev_destroy(h);
-    return fail(W2V_ERR_HIP, msg);
+  if (int rc = init_device(h)) {
+    delete h;
+    return rc;
   }
-  h->own_stream = true;
-  h->n_cu = ncu > 0 ? ncu : 256;
   h->d4 = (cfg->word_dim + 3) & ~3;
   h->nv = pick_nv(cfg->word_dim);
   h->pitch = (int64_t)h->nv * w2v::kWave;  // the kernels' row width (w2v_kernels.hpp, Row I/O)
@@ -346,31 +348,18 @@ int w2v_dev_create(const w2v_dev_config* cfg, w2v_dev** out) {
   return W2V_OK;
 }
 
-void w2v_dev_destroy(w2v_dev* h) {
-  if (!h) return;
-  (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  if (!h->model_bound) { dfree(h->W); dfree(h->C); dfree(h->S); }
-  dfree(h->keep); dfree(h->table); dfree(h->codes); dfree(h->points); dfree(h->coff);
-  release_corpus(h); dfree(h->replay); dfree(h->replay_off);
-  dfree(h->counters); dfree(h->work);
-  dfree(h->scratch_f); dfree(h->scratch_codes); dfree(h->xfer_f); dfree(h->wide_scratch); dfree(h->hot_sc_d);
-  if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
-}
+void w2v_dev_destroy(w2v_dev* h) { delete h; }
 
 int w2v_dev_set_stream(w2v_dev* h, void* s) {
   if (!h) return fail(W2V_ERR_ARG, "null handle");
   if (set_device(h)) return W2V_ERR_HIP;
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  if (h->own_stream) HIP_TRY(hipStreamDestroy(h->stream));
-  if (s) {
-    h->stream = (hipStream_t)s;
-    h->own_stream = false;
-  } else {
-    HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    h->own_stream = true;
-  }
+  W2V_HIP_TRY(hipStreamSynchronize(h->stream));
+  hipStream_t next = (hipStream_t)s;
+  if (!s) W2V_HIP_TRY(hipStreamCreateWithFlags(&next, hipStreamNonBlocking));
+  const hipStream_t old = h->own_stream ? h->stream : nullptr;
+  h->stream = next;  // the handle holds a live stream whatever the old one's destroy says
+  h->own_stream = !s;
+  if (old) W2V_HIP_TRY(hipStreamDestroy(old));
   return W2V_OK;
 }
 
@@ -395,7 +384,7 @@ int w2v_dev_upload_vocab(w2v_dev* h, int64_t V, const float* keep, const int64_t
   if (!h || !keep) return fail(W2V_ERR_ARG, "w2v_dev_upload_vocab: null argument");
   if (V < 1 || V > (int64_t)INT32_MAX) return fail(W2V_ERR_ARG, "vocab_size out of range");
   if (h->cfg.hs && V < 2) return fail(W2V_ERR_ARG, "hs needs vocab_size >= 2");
-  if (h->cfg.negative > 0 && !bounds && !h->table)
+  if (h->cfg.negative > 0 && !bounds && !h->table.get())
     return fail(W2V_ERR_ARG, "negative sampling needs table_bounds (or w2v_dev_upload_table first)");
   if (h->cfg.hs && (!codes || !points || !coff)) return fail(W2V_ERR_ARG, "hs needs codes/points/code_offsets");
   // validate everything before touching the handle, so a rejected call leaves it as it was
@@ -416,61 +405,47 @@ int w2v_dev_upload_vocab(w2v_dev* h, int64_t V, const float* keep, const int64_t
   }
   if (set_device(h)) return W2V_ERR_HIP;
   // device buffers first (a HIP failure leaves the handle's old vocab in place)
-  float* dkeep = nullptr;
-  uint32_t* dtable = nullptr;
-  int64_t* db = nullptr;
-  uint8_t* dcodes = nullptr;
-  int32_t* dpoints = nullptr;
-  int64_t* dcoff = nullptr;
-  auto drop = [&]() { dfree(dkeep); dfree(dtable); dfree(db); dfree(dcodes); dfree(dpoints); dfree(dcoff); };
-  hipError_t e = hipMalloc(&dkeep, V * sizeof(float));
-  if (e == hipSuccess) e = hipMemcpy(dkeep, keep, V * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess && h->cfg.negative > 0 && bounds) {
-    e = hipMalloc(&dtable, n * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(&db, (V + 1) * sizeof(int64_t));
-    if (e == hipSuccess) e = hipMemcpy(db, bounds, (V + 1) * sizeof(int64_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(w2v::expand_table_kernel, dim3(4096), dim3(256), 0, h->stream, db, V, dtable, n);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  w2v::DevBuf<float> dkeep;
+  w2v::DevBuf<uint32_t> dtable;
+  w2v::DevBuf<uint8_t> dcodes;
+  w2v::DevBuf<int32_t> dpoints;
+  w2v::DevBuf<int64_t> dcoff;
+  int rc = dkeep.alloc((size_t)V);
+  if (rc) return rc;
+  W2V_HIP_TRY(hipMemcpy(dkeep.get(), keep, V * sizeof(float), hipMemcpyHostToDevice));
+  if (h->cfg.negative > 0 && bounds) {
+    w2v::DevBuf<int64_t> db;
+    if ((rc = dtable.alloc((size_t)n)) || (rc = db.alloc((size_t)V + 1))) return rc;
+    W2V_HIP_TRY(hipMemcpy(db.get(), bounds, (V + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(w2v::expand_table_kernel, dim3(4096), dim3(256), 0, h->stream, db.get(), V, dtable.get(), n);
+    W2V_HIP_TRY(hipGetLastError());
+    W2V_HIP_TRY(hipStreamSynchronize(h->stream));
   }
   const int64_t nc = h->cfg.hs ? coff[V] : 0;
-  if (e == hipSuccess && h->cfg.hs) {
-    e = hipMalloc(&dcodes, (nc > 0 ? nc : 1));
-    if (e == hipSuccess) e = hipMalloc(&dpoints, (nc > 0 ? nc : 1) * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc(&dcoff, (V + 1) * sizeof(int64_t));
-    if (e == hipSuccess && nc > 0) e = hipMemcpy(dcodes, codes, nc, hipMemcpyHostToDevice);
-    if (e == hipSuccess && nc > 0) e = hipMemcpy(dpoints, points, nc * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dcoff, coff, (V + 1) * sizeof(int64_t), hipMemcpyHostToDevice);
+  if (h->cfg.hs) {
+    const size_t n1 = (size_t)(nc > 0 ? nc : 1);
+    if ((rc = dcodes.alloc(n1)) || (rc = dpoints.alloc(n1)) || (rc = dcoff.alloc((size_t)V + 1))) return rc;
+    if (nc > 0) W2V_HIP_TRY(hipMemcpy(dcodes.get(), codes, nc, hipMemcpyHostToDevice));
+    if (nc > 0) W2V_HIP_TRY(hipMemcpy(dpoints.get(), points, nc * sizeof(int32_t), hipMemcpyHostToDevice));
+    W2V_HIP_TRY(hipMemcpy(dcoff.get(), coff, (V + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
   }
-  if (e != hipSuccess) {
-    drop();
-    return fail(W2V_ERR_HIP, std::string("w2v_dev_upload_vocab: ") + hipGetErrorString(e));
-  }
-  dfree(db);
   if (h->V != V) {
-    if (!h->model_bound) { dfree(h->W); dfree(h->C); dfree(h->S); }
-    h->W = h->C = h->S = nullptr;
-    h->model_bound = false;
+    h->drop_model();
     h->pitch = (int64_t)h->nv * w2v::kWave;
     h->model_ready = false;
     h->tok_count.clear();  // the corpus statistics refer to the old ids
   }
   h->V = V;
   ++h->data_version;
-  dfree(h->keep);
-  h->keep = dkeep;
+  h->keep = std::move(dkeep);
   h->keep_h.assign(keep, keep + V);
-  if (dtable) {
-    dfree(h->table);
-    h->table = dtable;
+  if (dtable.get()) {
+    h->table = std::move(dtable);
     h->stats.table_frac.assign((size_t)V, 0.0);
     for (size_t r = 0; r < h->stats.table_frac.size(); ++r) h->stats.table_frac[r] = (double)(bounds[r + 1] - bounds[r]) / (double)n;
   }
   if (h->cfg.hs) {
-    dfree(h->codes); dfree(h->points); dfree(h->coff);
-    h->codes = dcodes; h->points = dpoints; h->coff = dcoff;
+    h->codes = std::move(dcodes), h->points = std::move(dpoints), h->coff = std::move(dcoff);
     h->n_codes = nc;
     // the tree's shape, for the per-node statistics: paths run root -> leaf
     h->leaf_node.assign((size_t)V, -1);
@@ -492,9 +467,10 @@ int w2v_dev_upload_table(w2v_dev* h, const uint32_t* table, int64_t n) {
   if (!h || !table) return fail(W2V_ERR_ARG, "w2v_dev_upload_table: null argument");
   if (n != h->cfg.table_size) return fail(W2V_ERR_ARG, "table length != table_size");
   if (set_device(h)) return W2V_ERR_HIP;
-  dfree(h->table);
-  HIP_TRY(hipMalloc(&h->table, n * sizeof(uint32_t)));
-  HIP_TRY(hipMemcpy(h->table, table, n * sizeof(uint32_t), hipMemcpyHostToDevice));
+  w2v::DevBuf<uint32_t> t;
+  if (int rc = t.alloc((size_t)n)) return rc;
+  W2V_HIP_TRY(hipMemcpy(t.get(), table, n * sizeof(uint32_t), hipMemcpyHostToDevice));
+  h->table = std::move(t);
   h->stats.table_frac.assign((size_t)std::max<int64_t>(h->V, 0), 0.0);
   for (int64_t i = 0; i < n; ++i)
     if ((int64_t)table[i] < h->V) h->stats.table_frac[table[i]] += 1.0 / (double)n;
@@ -502,23 +478,24 @@ int w2v_dev_upload_table(w2v_dev* h, const uint32_t* table, int64_t n) {
   return W2V_OK;
 }
 
+// A zeroed matrix of n floats owned by the handle, unless it views one already.
+static int ensure_matrix(w2v::DevBuf<float>& own, float*& view, size_t n) {
+  if (view) return W2V_OK;
+  w2v::DevBuf<float> m;
+  if (int rc = m.alloc(n)) return rc;
+  W2V_HIP_TRY(hipMemset(m.get(), 0, n * sizeof(float)));
+  own = std::move(m);
+  view = own.get();
+  return W2V_OK;
+}
+
 static int ensure_model(w2v_dev* h) {
   if (h->V < 1) return fail(W2V_ERR_STATE, "upload the vocab before the model");
-  const size_t rows_bytes = (size_t)h->V * h->pitch * sizeof(float);
-  if (!h->W) {
-    HIP_TRY(hipMalloc(&h->W, rows_bytes));
-    HIP_TRY(hipMemset(h->W, 0, rows_bytes));
-  }
-  if (h->need_C && !h->C) {
-    HIP_TRY(hipMalloc(&h->C, rows_bytes));
-    HIP_TRY(hipMemset(h->C, 0, rows_bytes));
-  }
-  if (h->need_S && !h->S) {
-    const size_t sb = (size_t)(h->V > 1 ? h->V - 1 : 1) * h->pitch * sizeof(float);
-    HIP_TRY(hipMalloc(&h->S, sb));
-    HIP_TRY(hipMemset(h->S, 0, sb));
-  }
-  return W2V_OK;
+  const size_t rows = (size_t)h->V * h->pitch;
+  int rc = ensure_matrix(h->W_own, h->W, rows);
+  if (!rc && h->need_C) rc = ensure_matrix(h->C_own, h->C, rows);
+  if (!rc && h->need_S) rc = ensure_matrix(h->S_own, h->S, (size_t)(h->V > 1 ? h->V - 1 : 1) * h->pitch);
+  return rc;
 }
 
 int w2v_dev_upload_model(w2v_dev* h, const float* W, const float* C, const float* S) {
@@ -528,15 +505,15 @@ int w2v_dev_upload_model(w2v_dev* h, const float* W, const float* C, const float
   int rc = ensure_model(h);
   if (rc) return rc;
   const size_t d = (size_t)h->cfg.word_dim, dp = (size_t)h->pitch * sizeof(float);
-  if (W) HIP_TRY(hipMemcpy2D(h->W, dp, W, d * sizeof(float), d * sizeof(float), h->V, hipMemcpyHostToDevice));
+  if (W) W2V_HIP_TRY(hipMemcpy2D(h->W, dp, W, d * sizeof(float), d * sizeof(float), h->V, hipMemcpyHostToDevice));
   if (C) {
     if (!h->C) return fail(W2V_ERR_ARG, "C is not used by this configuration");
-    HIP_TRY(hipMemcpy2D(h->C, dp, C, d * sizeof(float), d * sizeof(float), h->V, hipMemcpyHostToDevice));
+    W2V_HIP_TRY(hipMemcpy2D(h->C, dp, C, d * sizeof(float), d * sizeof(float), h->V, hipMemcpyHostToDevice));
   }
   if (S) {
     if (!h->S) return fail(W2V_ERR_ARG, "synapses1 is not used by this configuration");
     if (h->V > 1)
-      HIP_TRY(hipMemcpy2D(h->S, dp, S, d * sizeof(float), d * sizeof(float), h->V - 1, hipMemcpyHostToDevice));
+      W2V_HIP_TRY(hipMemcpy2D(h->S, dp, S, d * sizeof(float), d * sizeof(float), h->V - 1, hipMemcpyHostToDevice));
   }
   h->model_ready = true;
   return W2V_OK;
@@ -547,12 +524,12 @@ int w2v_dev_download_model(w2v_dev* h, float* W, float* C, float* S) {
   if (!h) return fail(W2V_ERR_ARG, "null handle");
   if (!h->W) return fail(W2V_ERR_STATE, "no model on the device");
   if (set_device(h)) return W2V_ERR_HIP;
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  W2V_HIP_TRY(hipStreamSynchronize(h->stream));
   const size_t d = (size_t)h->cfg.word_dim, dp = (size_t)h->pitch * sizeof(float);
-  if (W) HIP_TRY(hipMemcpy2D(W, d * sizeof(float), h->W, dp, d * sizeof(float), h->V, hipMemcpyDeviceToHost));
-  if (C && h->C) HIP_TRY(hipMemcpy2D(C, d * sizeof(float), h->C, dp, d * sizeof(float), h->V, hipMemcpyDeviceToHost));
+  if (W) W2V_HIP_TRY(hipMemcpy2D(W, d * sizeof(float), h->W, dp, d * sizeof(float), h->V, hipMemcpyDeviceToHost));
+  if (C && h->C) W2V_HIP_TRY(hipMemcpy2D(C, d * sizeof(float), h->C, dp, d * sizeof(float), h->V, hipMemcpyDeviceToHost));
   if (S && h->S && h->V > 1)
-    HIP_TRY(hipMemcpy2D(S, d * sizeof(float), h->S, dp, d * sizeof(float), h->V - 1, hipMemcpyDeviceToHost));
+    W2V_HIP_TRY(hipMemcpy2D(S, d * sizeof(float), h->S, dp, d * sizeof(float), h->V - 1, hipMemcpyDeviceToHost));
   return W2V_OK;
 }
 
@@ -615,47 +592,38 @@ int w2v_dev_model_max_diff(w2v_dev* a, w2v_dev* b, float* out) {
       !a->S != !b->S)
     return fail(W2V_ERR_ARG, "the two handles hold models of different shapes");
   if (set_device(b)) return W2V_ERR_HIP;
-  HIP_TRY(hipStreamSynchronize(b->stream));
+  W2V_HIP_TRY(hipStreamSynchronize(b->stream));
   if (set_device(a)) return W2V_ERR_HIP;
-  HIP_TRY(hipStreamSynchronize(a->stream));
+  W2V_HIP_TRY(hipStreamSynchronize(a->stream));
   const float* MA[3] = {a->W, a->C, a->S};
   const float* MB[3] = {b->W, b->C, b->S};
   const int64_t rows[3] = {a->V, a->V, a->V - 1};
-  unsigned int* acc = nullptr;
-  float* stage = nullptr;  // b's matrix on a's device when they differ
-  int rc = W2V_OK;
-  if (hipMalloc(&acc, 6 * sizeof(unsigned int)) != hipSuccess) return fail(W2V_ERR_HIP, "max_diff: hipMalloc");
-  if (hipMemset(acc, 0, 6 * sizeof(unsigned int)) != hipSuccess) rc = fail(W2V_ERR_HIP, "max_diff: memset");
-  for (int k = 0; k < 3 && rc == W2V_OK; ++k) {
+  w2v::DevBuf<unsigned int> acc;
+  w2v::DevBuf<float> stage;  // b's matrix on a's device when they differ
+  if (int rc = acc.alloc(6)) return rc;
+  W2V_HIP_TRY(hipMemset(acc.get(), 0, 6 * sizeof(unsigned int)));
+  for (int k = 0; k < 3; ++k) {
     if (!MA[k] || rows[k] <= 0) continue;
     const size_t bytes = (size_t)rows[k] * (size_t)a->pitch * sizeof(float);
     const float* B = MB[k];
     if (a->device != b->device) {
-      if (!stage && hipMalloc(&stage, (size_t)a->V * (size_t)a->pitch * sizeof(float)) != hipSuccess) {
-        rc = fail(W2V_ERR_HIP, "max_diff: staging buffer");
-        break;
-      }
-      if (hipMemcpyPeer(stage, a->device, B, b->device, bytes) != hipSuccess) {
-        rc = fail(W2V_ERR_HIP, "max_diff: peer copy");
-        break;
-      }
-      B = stage;
+      if (!stage.get())
+        if (int rc = stage.alloc((size_t)a->V * (size_t)a->pitch)) return rc;
+      W2V_HIP_TRY(hipMemcpyPeer(stage.get(), a->device, B, b->device, bytes));
+      B = stage.get();
     }
     hipLaunchKernelGGL(w2v::max_diff_kernel, dim3(2048), dim3(256), 0, a->stream, MA[k], B, rows[k], a->pitch,
-                       a->cfg.word_dim, acc + 2 * k);
-    if (hipGetLastError() != hipSuccess) rc = fail(W2V_ERR_HIP, "max_diff_kernel launch");
-    if (rc == W2V_OK && hipStreamSynchronize(a->stream) != hipSuccess) rc = fail(W2V_ERR_HIP, "max_diff sync");
+                       a->cfg.word_dim, acc.get() + 2 * k);
+    W2V_HIP_TRY(hipGetLastError());
+    W2V_HIP_TRY(hipStreamSynchronize(a->stream));
   }
   unsigned int host[6] = {0, 0, 0, 0, 0, 0};
-  if (rc == W2V_OK && hipMemcpy(host, acc, sizeof(host), hipMemcpyDeviceToHost) != hipSuccess)
-    rc = fail(W2V_ERR_HIP, "max_diff copy");
-  (void)hipFree(acc);
-  if (stage) (void)hipFree(stage);
+  W2V_HIP_TRY(hipMemcpy(host, acc.get(), sizeof(host), hipMemcpyDeviceToHost));
   for (int k = 0; k < 3; ++k) {  // acc holds (max |A - B|, max |A|) per matrix
     std::memcpy(&out[k], &host[2 * k], sizeof(float));
     std::memcpy(&out[3 + k], &host[2 * k + 1], sizeof(float));
   }
-  return rc;
+  return W2V_OK;
 }
 
 // Row-sparse transfer between host rows and one resident matrix: the per-call
@@ -674,26 +642,23 @@ static int transfer_rows(w2v_dev* h, int32_t which, const int32_t* rows, int64_t
   if (n == 0) return W2V_OK;
   const int d = h->cfg.word_dim;
   const int64_t need = n * d + n + 1;  // packed rows, then the row ids (int32 in float slots)
-  if (h->xfer_n < need) {
-    dfree(h->xfer_f);
-    HIP_TRY(hipMalloc(&h->xfer_f, need * sizeof(float)));
-    h->xfer_n = need;
-  }
-  float* packed = h->xfer_f;
-  int32_t* drows = reinterpret_cast<int32_t*>(h->xfer_f + n * d);
-  HIP_TRY(hipMemcpyAsync(drows, rows, n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+  if ((int64_t)h->xfer_f.size() < need)
+    if (int rc = h->xfer_f.alloc((size_t)need)) return rc;
+  float* packed = h->xfer_f.get();
+  int32_t* drows = reinterpret_cast<int32_t*>(packed + n * d);
+  W2V_HIP_TRY(hipMemcpyAsync(drows, rows, n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
   if (up) {
-    HIP_TRY(hipMemcpyAsync(packed, data, (size_t)n * d * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    W2V_HIP_TRY(hipMemcpyAsync(packed, data, (size_t)n * d * sizeof(float), hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(w2v::scatter_rows_kernel, dim3((unsigned)n), dim3(256), 0, h->stream, M, h->pitch, d, drows, n,
                        packed);
-    HIP_TRY(hipGetLastError());
+    W2V_HIP_TRY(hipGetLastError());
   } else {
     hipLaunchKernelGGL(w2v::gather_rows_kernel, dim3((unsigned)n), dim3(256), 0, h->stream, M, h->pitch, d, drows, n,
                        packed);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(data, packed, (size_t)n * d * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    W2V_HIP_TRY(hipGetLastError());
+    W2V_HIP_TRY(hipMemcpyAsync(data, packed, (size_t)n * d * sizeof(float), hipMemcpyDeviceToHost, h->stream));
   }
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  W2V_HIP_TRY(hipStreamSynchronize(h->stream));
   h->model_ready = true;
   return W2V_OK;
 }
@@ -716,12 +681,11 @@ int w2v_dev_bind_model(w2v_dev* h, float* dW, float* dC, float* dS, int64_t pitc
   if (h->need_S && !dS) return fail(W2V_ERR_ARG, "this configuration needs synapses1");
   for (const float* p : {dW, dC, dS})
     if (p && (reinterpret_cast<uintptr_t>(p) & 15u)) return fail(W2V_ERR_ARG, "matrix base must be 16-B aligned");
-  if (!h->model_bound) { dfree(h->W); dfree(h->C); dfree(h->S); }
+  h->drop_model();
   h->W = dW;
   h->C = h->need_C ? dC : nullptr;
   h->S = h->need_S ? dS : nullptr;
   h->pitch = pitch;
-  h->model_bound = true;
   h->model_ready = true;
   return W2V_OK;
 }
@@ -758,31 +722,19 @@ int w2v_dev_upload_corpus(w2v_dev* h, const int32_t* ids, int64_t n_tok, const i
     max_len = std::max<int64_t>(max_len, soff[s + 1] - soff[s]);
   }
   if (h->V < 1) return fail(W2V_ERR_STATE, "upload the vocab before the corpus");
-  std::vector<int64_t> hist((size_t)h->V, 0);  // also the flush-scale statistics (priv_scales)
+  std::vector<int64_t> hist((size_t)h->V, 0);
   for (int64_t t = 0; t < n_tok; ++t) {
     if (ids[t] < 0 || ids[t] >= h->V) return fail(W2V_ERR_ARG, "token id out of vocab range");
     ++hist[(size_t)ids[t]];
   }
   if (train_words <= 0 && n_tok > 0) return fail(W2V_ERR_ARG, "train_words must be > 0");
   if (set_device(h)) return W2V_ERR_HIP;
-  release_corpus(h);
-  h->corpus = new CorpusBuf();
-  HIP_TRY(hipMalloc(&h->corpus->ids, (n_tok > 0 ? n_tok : 1) * sizeof(int32_t)));
-  HIP_TRY(hipMalloc(&h->corpus->soff, (n_sent + 1) * sizeof(int64_t)));
-  h->ids = h->corpus->ids;
-  h->soff = h->corpus->soff;
-  if (n_tok > 0) HIP_TRY(hipMemcpy(h->ids, ids, n_tok * sizeof(int32_t), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(h->soff, soff, (n_sent + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
-  HIP_TRY(hipMalloc(&h->order, (n_sent > 0 ? n_sent : 1) * sizeof(int64_t)));
-  h->n_tok = n_tok;
-  h->n_sent = n_sent;
-  h->n_order = 0;
-  h->max_len = max_len;
-  h->train_words = train_words;
-  h->tok_count.swap(hist);
-  ++h->data_version;
-  h->corpus_ready = true;
-  return W2V_OK;
+  auto c = std::make_shared<CorpusBuf>();
+  int rc;
+  if ((rc = c->ids.alloc((size_t)(n_tok > 0 ? n_tok : 1))) || (rc = c->soff.alloc((size_t)n_sent + 1))) return rc;
+  if (n_tok > 0) W2V_HIP_TRY(hipMemcpy(c->ids.get(), ids, n_tok * sizeof(int32_t), hipMemcpyHostToDevice));
+  W2V_HIP_TRY(hipMemcpy(c->soff.get(), soff, (n_sent + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+  return install_corpus(h, std::move(c), n_tok, n_sent, max_len, train_words, std::move(hist));
 }
 
 int w2v_dev_adopt_corpus(w2v_dev* h, w2v_ingest* g) {
@@ -797,7 +749,7 @@ int w2v_dev_adopt_corpus(w2v_dev* h, w2v_ingest* g) {
   if (v.train_words <= 0 && v.n_ids > 0) return fail(W2V_ERR_ARG, "train_words must be > 0");
   if (set_device(h)) return W2V_ERR_HIP;
   std::vector<int64_t> soff((size_t)v.n_sentences + 1);
-  HIP_TRY(hipMemcpy(soff.data(), v.offsets, soff.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+  W2V_HIP_TRY(hipMemcpy(soff.data(), v.offsets, soff.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
   if (soff[0] != 0 || soff.back() != v.n_ids) return fail(W2V_ERR_STATE, "ingest offsets do not span its ids");
   int64_t max_len = 0;
   for (int64_t s = 0; s < v.n_sentences; ++s) {
@@ -806,24 +758,12 @@ int w2v_dev_adopt_corpus(w2v_dev* h, w2v_ingest* g) {
   }
   std::vector<int64_t> hist((size_t)h->V, 0);
   for (int64_t w = 0; w < v.n_vocab; ++w) hist[(size_t)w] = v.hist[w];
-  release_corpus(h);
-  h->corpus = new CorpusBuf();
-  HIP_TRY(hipMalloc(&h->corpus->ids, (v.n_ids > 0 ? v.n_ids : 1) * sizeof(int32_t)));
-  HIP_TRY(hipMalloc(&h->corpus->soff, (v.n_sentences + 1) * sizeof(int64_t)));
-  h->ids = h->corpus->ids;
-  h->soff = h->corpus->soff;
-  if (v.n_ids > 0) HIP_TRY(hipMemcpy(h->ids, v.ids, v.n_ids * sizeof(int32_t), hipMemcpyDeviceToDevice));
-  HIP_TRY(hipMemcpy(h->soff, v.offsets, (v.n_sentences + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice));
-  HIP_TRY(hipMalloc(&h->order, (v.n_sentences > 0 ? v.n_sentences : 1) * sizeof(int64_t)));
-  h->n_tok = v.n_ids;
-  h->n_sent = v.n_sentences;
-  h->n_order = 0;
-  h->max_len = max_len;
-  h->train_words = v.train_words;
-  h->tok_count.swap(hist);
-  ++h->data_version;
-  h->corpus_ready = true;
-  return W2V_OK;
+  auto c = std::make_shared<CorpusBuf>();
+  int rc;
+  if ((rc = c->ids.alloc((size_t)(v.n_ids > 0 ? v.n_ids : 1))) || (rc = c->soff.alloc(soff.size()))) return rc;
+  if (v.n_ids > 0) W2V_HIP_TRY(hipMemcpy(c->ids.get(), v.ids, v.n_ids * sizeof(int32_t), hipMemcpyDeviceToDevice));
+  W2V_HIP_TRY(hipMemcpy(c->soff.get(), v.offsets, soff.size() * sizeof(int64_t), hipMemcpyDeviceToDevice));
+  return install_corpus(h, std::move(c), v.n_ids, v.n_sentences, max_len, v.train_words, std::move(hist));
 }
 
 int w2v_dev_share_corpus(w2v_dev* h, w2v_dev* src) {
@@ -833,23 +773,9 @@ int w2v_dev_share_corpus(w2v_dev* h, w2v_dev* src) {
   if (src->device != h->device) return fail(W2V_ERR_ARG, "w2v_dev_share_corpus: the source is on another device");
   if (h->V != src->V) return fail(W2V_ERR_ARG, "w2v_dev_share_corpus: the vocabularies differ");
   if (set_device(h)) return W2V_ERR_HIP;
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  W2V_HIP_TRY(hipStreamSynchronize(h->stream));
   if (h->corpus == src->corpus) return W2V_OK;
-  release_corpus(h);
-  HIP_TRY(hipMalloc(&h->order, (src->n_sent > 0 ? src->n_sent : 1) * sizeof(int64_t)));
-  h->corpus = src->corpus;
-  ++h->corpus->refs;
-  h->ids = src->ids;
-  h->soff = src->soff;
-  h->n_tok = src->n_tok;
-  h->n_sent = src->n_sent;
-  h->n_order = 0;
-  h->max_len = src->max_len;
-  h->train_words = src->train_words;
-  h->tok_count = src->tok_count;
-  ++h->data_version;
-  h->corpus_ready = true;
-  return W2V_OK;
+  return install_corpus(h, src->corpus, src->n_tok, src->n_sent, src->max_len, src->train_words, src->tok_count);
 }
 
 int w2v_dev_upload_replay(w2v_dev* h, const uint32_t* stream, int64_t n, const int64_t* off,
@@ -858,11 +784,13 @@ int w2v_dev_upload_replay(w2v_dev* h, const uint32_t* stream, int64_t n, const i
   for (int64_t k = 0; k < n_off; ++k)
     if (off[k] < 0 || off[k] > n) return fail(W2V_ERR_ARG, "replay offset out of range");
   if (set_device(h)) return W2V_ERR_HIP;
-  dfree(h->replay); dfree(h->replay_off);
-  HIP_TRY(hipMalloc(&h->replay, (n > 0 ? n : 1) * sizeof(uint32_t)));
-  if (n > 0) HIP_TRY(hipMemcpy(h->replay, stream, n * sizeof(uint32_t), hipMemcpyHostToDevice));
-  HIP_TRY(hipMalloc(&h->replay_off, (n_off > 0 ? n_off : 1) * sizeof(int64_t)));
-  if (n_off > 0) HIP_TRY(hipMemcpy(h->replay_off, off, n_off * sizeof(int64_t), hipMemcpyHostToDevice));
+  w2v::DevBuf<uint32_t> r;
+  w2v::DevBuf<int64_t> ro;
+  int rc;
+  if ((rc = r.alloc((size_t)(n > 0 ? n : 1))) || (rc = ro.alloc((size_t)(n_off > 0 ? n_off : 1)))) return rc;
+  if (n > 0) W2V_HIP_TRY(hipMemcpy(r.get(), stream, n * sizeof(uint32_t), hipMemcpyHostToDevice));
+  if (n_off > 0) W2V_HIP_TRY(hipMemcpy(ro.get(), off, n_off * sizeof(int64_t), hipMemcpyHostToDevice));
+  h->replay = std::move(r), h->replay_off = std::move(ro);
   h->n_replay_off = n_off;
   return W2V_OK;
 }
@@ -871,8 +799,8 @@ int w2v_dev_set_progress(w2v_dev* h, int64_t cw) {
   if (!h) return fail(W2V_ERR_ARG, "null handle");
   if (set_device(h)) return W2V_ERR_HIP;
   unsigned long long v = (unsigned long long)cw;
-  HIP_TRY(hipMemcpyAsync(h->counters, &v, sizeof(v), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  W2V_HIP_TRY(hipMemcpyAsync(h->counters.get(), &v, sizeof(v), hipMemcpyHostToDevice, h->stream));
+  W2V_HIP_TRY(hipStreamSynchronize(h->stream));
   return W2V_OK;
 }
 
@@ -884,8 +812,8 @@ int w2v_dev_set_progress_async(w2v_dev* h, int64_t cw) {
   if (!h) return fail(W2V_ERR_ARG, "null handle");
   if (cw < 0) return fail(W2V_ERR_ARG, "current_words must be >= 0");
   if (set_device(h)) return W2V_ERR_HIP;
-  hipLaunchKernelGGL(w2v::set_counter_kernel, dim3(1), dim3(1), 0, h->stream, h->counters, (unsigned long long)cw);
-  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(w2v::set_counter_kernel, dim3(1), dim3(1), 0, h->stream, h->counters.get(), (unsigned long long)cw);
+  W2V_HIP_TRY(hipGetLastError());
   return W2V_OK;
 }
 
@@ -901,8 +829,8 @@ int w2v_dev_get_progress(w2v_dev* h, int64_t* cw) {
   if (!h || !cw) return fail(W2V_ERR_ARG, "null argument");
   if (set_device(h)) return W2V_ERR_HIP;
   unsigned long long v = 0;
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  HIP_TRY(hipMemcpy(&v, h->counters, sizeof(v), hipMemcpyDeviceToHost));
+  W2V_HIP_TRY(hipStreamSynchronize(h->stream));
+  W2V_HIP_TRY(hipMemcpy(&v, h->counters.get(), sizeof(v), hipMemcpyDeviceToHost));
   *cw = (int64_t)v;
   return W2V_OK;
 }
@@ -934,8 +862,8 @@ int w2v_dev_set_order(w2v_dev* h, const int64_t* order, int64_t n) {
   for (int64_t k = 0; k < n; ++k)
     if (order[k] < 0 || order[k] >= h->n_sent) return fail(W2V_ERR_ARG, "order entry out of range");
   if (set_device(h)) return W2V_ERR_HIP;
-  HIP_TRY(hipStreamSynchronize(h->stream));  // a slice enqueued before may still read the old order
-  if (n > 0) HIP_TRY(hipMemcpy(h->order, order, n * sizeof(int64_t), hipMemcpyHostToDevice));
+  W2V_HIP_TRY(hipStreamSynchronize(h->stream));  // a slice enqueued before may still read the old order
+  if (n > 0) W2V_HIP_TRY(hipMemcpy(h->order.get(), order, n * sizeof(int64_t), hipMemcpyHostToDevice));
   h->n_order = n;
   return W2V_OK;
 }
@@ -944,7 +872,7 @@ int w2v_dev_train_slice_async(w2v_dev* h, int32_t epoch, int64_t first, int64_t 
   if (!h) return fail(W2V_ERR_ARG, "null handle");
   if (first < 0 || count < 0 || first + count > h->n_order)
     return fail(W2V_ERR_ARG, "slice outside the order set with w2v_dev_set_order");
-  return launch_train(h, epoch, h->order + first, count);
+  return launch_train(h, epoch, h->order.get() + first, count);
 }
 
 int w2v_dev_train_sentences_async(w2v_dev* h, int32_t epoch, const int64_t* order_dev, int64_t count) {
@@ -969,28 +897,22 @@ static w2v::PolicyInput policy_input(w2v_dev* h, int64_t count, int sn_waves) {
 static int launch_buffers(w2v_dev* h, const w2v::LaunchPlan& p, w2v::TrainArgs& a) {
   if (!p.hot_sc.empty()) {  // the atomic hot Huffman nodes' scales
     const int64_t nodes = (int64_t)p.hot_sc.size();
-    if (p.hot_sc != h->hot_sc_h || !h->hot_sc_d) {
-      HIP_TRY(hipStreamSynchronize(h->stream));  // an earlier launch may still read the old scales
-      if (nodes > h->hot_sc_cap) {
-        dfree(h->hot_sc_d);
-        h->hot_sc_cap = 0;
-        HIP_TRY(hipMalloc(&h->hot_sc_d, (size_t)nodes * sizeof(float)));
-        h->hot_sc_cap = nodes;
-      }
-      HIP_TRY(hipMemcpy(h->hot_sc_d, p.hot_sc.data(), (size_t)nodes * sizeof(float), hipMemcpyHostToDevice));
+    if (p.hot_sc != h->hot_sc_h || !h->hot_sc_d.get()) {
+      W2V_HIP_TRY(hipStreamSynchronize(h->stream));  // an earlier launch may still read the old scales
+      h->hot_sc_h.clear();  // until the copy below has landed
+      if (nodes > (int64_t)h->hot_sc_d.size())
+        if (int rc = h->hot_sc_d.alloc((size_t)nodes)) return rc;
+      W2V_HIP_TRY(hipMemcpy(h->hot_sc_d.get(), p.hot_sc.data(), (size_t)nodes * sizeof(float), hipMemcpyHostToDevice));
       h->hot_sc_h = p.hot_sc;
     }
-    a.hot_sc = h->hot_sc_d;
+    a.hot_sc = h->hot_sc_d.get();
   }
   if (p.wide_scratch > 0) {  // cbow_center_huge: one id slice per wave
-    if (p.wide_scratch > h->wide_scratch_n) {
-      HIP_TRY(hipStreamSynchronize(h->stream));  // an earlier launch may still use the old slices
-      dfree(h->wide_scratch);
-      h->wide_scratch_n = 0;
-      HIP_TRY(hipMalloc(&h->wide_scratch, (size_t)p.wide_scratch * sizeof(int32_t)));
-      h->wide_scratch_n = p.wide_scratch;
+    if (p.wide_scratch > (int64_t)h->wide_scratch.size()) {
+      W2V_HIP_TRY(hipStreamSynchronize(h->stream));  // an earlier launch may still use the old slices
+      if (int rc = h->wide_scratch.alloc((size_t)p.wide_scratch)) return rc;
     }
-    a.wide_ids = h->wide_scratch;
+    a.wide_ids = h->wide_scratch.get();
     a.wide_stride = p.wide_stride;
   }
   return W2V_OK;
@@ -1000,9 +922,9 @@ static int launch_train(w2v_dev* h, int32_t epoch, const int64_t* order_dev, int
   w2v::Range range_("w2v launch");
   if (!h->vocab_ready || !h->corpus_ready) return fail(W2V_ERR_STATE, "upload vocab and corpus first");
   if (!h->model_ready) return fail(W2V_ERR_STATE, "upload the model first");
-  if (h->cfg.negative > 0 && !h->table) return fail(W2V_ERR_STATE, "no unigram table on the device");
+  if (h->cfg.negative > 0 && !h->table.get()) return fail(W2V_ERR_STATE, "no unigram table on the device");
   if (h->rng == W2V_RNG_REPLAY) {
-    if (!h->replay) return fail(W2V_ERR_STATE, "replay mode without a replay stream");
+    if (!h->replay.get()) return fail(W2V_ERR_STATE, "replay mode without a replay stream");
     if ((int64_t)(epoch + 1) * h->n_sent > h->n_replay_off)
       return fail(W2V_ERR_ARG, "replay offsets do not cover this epoch");
   }
@@ -1025,19 +947,19 @@ static int launch_train(w2v_dev* h, int32_t epoch, const int64_t* order_dev, int
   a.window = h->cfg.window; a.negative = h->cfg.negative; a.cbow_mean = h->cfg.cbow_mean;
   a.iter = h->cfg.iter; a.init_alpha = h->cfg.init_alpha; a.min_alpha = h->cfg.min_alpha;
   a.train_words = (double)h->train_words;
-  a.ids = h->ids; a.soff = h->soff; a.order = order_dev; a.n_sent = count; a.n_corpus = h->n_sent;
-  a.keep = h->keep; a.table = h->table; a.table_size = h->cfg.table_size;
-  a.codes = h->codes; a.points = h->points; a.coff = h->coff;
-  a.replay = h->replay;
-  a.replay_off = h->replay_off ? h->replay_off + (int64_t)epoch * h->n_sent : nullptr;
-  a.words = h->counters;
-  a.work = h->work;
-  a.stats = h->counters + 1;
+  a.ids = h->corpus->ids.get(); a.soff = h->corpus->soff.get(); a.order = order_dev; a.n_sent = count; a.n_corpus = h->n_sent;
+  a.keep = h->keep.get(); a.table = h->table.get(); a.table_size = h->cfg.table_size;
+  a.codes = h->codes.get(); a.points = h->points.get(); a.coff = h->coff.get();
+  a.replay = h->replay.get();
+  a.replay_off = h->replay_off.get() ? h->replay_off.get() + (int64_t)epoch * h->n_sent : nullptr;
+  a.words = h->counters.get();
+  a.work = h->work.get();
+  a.stats = h->counters.get() + 1;
   a.key0 = (uint32_t)h->seed; a.key1 = (uint32_t)(h->seed >> 32);
   a.epoch = (uint32_t)epoch;
   a.fixed_alpha = h->fixed_alpha;
   a.strict = h->sched == W2V_SCHED_SEQUENTIAL ? 1 : 0;
-  HIP_TRY(hipMemsetAsync(h->work, 0, sizeof(unsigned int), h->stream));  // runs while the host plans
+  W2V_HIP_TRY(hipMemsetAsync(h->work.get(), 0, sizeof(unsigned int), h->stream));  // runs while the host plans
   // the policy (w2v_policy.cpp) decides the rest
   const KernelFn occ_fn = sn_fn ? sn_fn : kernel_for(h), deep_fn = sn_fn ? sn_fn : kernel_deep_for(h);
   hipError_t occ_err = hipSuccess;
@@ -1071,7 +993,7 @@ static int launch_train(w2v_dev* h, int32_t epoch, const int64_t* order_dev, int
   const size_t lds_bytes = (size_t)p.lds_bytes;
   h->last_plan = std::move(p);
   hipLaunchKernelGGL(fn, grid, block, lds_bytes, h->stream, a);
-  HIP_TRY(hipGetLastError());
+  W2V_HIP_TRY(hipGetLastError());
   return W2V_OK;
 }
 
@@ -1088,13 +1010,13 @@ int w2v_dev_train_epoch(w2v_dev* h, int32_t epoch, const int64_t* order, w2v_dev
     for (int64_t k = 0; k < h->n_sent; ++k)
       if (order[k] < 0 || order[k] >= h->n_sent) return fail(W2V_ERR_ARG, "order entry out of range");
     if (set_device(h)) return W2V_ERR_HIP;
-    HIP_TRY(hipMemcpyAsync(h->order, order, h->n_sent * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-    od = h->order;
+    W2V_HIP_TRY(hipMemcpyAsync(h->order.get(), order, h->n_sent * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    od = h->order.get();
     h->n_order = h->n_sent;
   }
   int rc = w2v_dev_train_epoch_async(h, epoch, od);
   if (rc) return rc;
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  W2V_HIP_TRY(hipStreamSynchronize(h->stream));
   w2v_dev_stats after{};
   rc = w2v_dev_read_stats(h, &after);
   if (rc) return rc;
@@ -1118,7 +1040,7 @@ int w2v_dev_synchronize(w2v_dev* h) {
   w2v::Range range_("w2v_dev_synchronize");
   if (!h) return fail(W2V_ERR_ARG, "null handle");
   if (set_device(h)) return W2V_ERR_HIP;
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  W2V_HIP_TRY(hipStreamSynchronize(h->stream));
   return W2V_OK;
 }
 
@@ -1126,8 +1048,8 @@ int w2v_dev_read_stats(w2v_dev* h, w2v_dev_stats* st) {
   if (!h || !st) return fail(W2V_ERR_ARG, "null argument");
   if (set_device(h)) return W2V_ERR_HIP;
   unsigned long long c[8];
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  HIP_TRY(hipMemcpy(c, h->counters, sizeof(c), hipMemcpyDeviceToHost));
+  W2V_HIP_TRY(hipStreamSynchronize(h->stream));
+  W2V_HIP_TRY(hipMemcpy(c, h->counters.get(), sizeof(c), hipMemcpyDeviceToHost));
   st->words = (int64_t)c[0];
   st->centers = (int64_t)c[1];
   st->contexts = (int64_t)c[2];
@@ -1141,8 +1063,8 @@ int w2v_dev_read_stats(w2v_dev* h, w2v_dev_stats* st) {
 int w2v_dev_reset_stats(w2v_dev* h) {
   if (!h) return fail(W2V_ERR_ARG, "null handle");
   if (set_device(h)) return W2V_ERR_HIP;
-  HIP_TRY(hipMemsetAsync(h->counters + 1, 0, 7 * sizeof(unsigned long long), h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  W2V_HIP_TRY(hipMemsetAsync(h->counters.get() + 1, 0, 7 * sizeof(unsigned long long), h->stream));
+  W2V_HIP_TRY(hipStreamSynchronize(h->stream));
   return W2V_OK;
 }
 
@@ -1294,31 +1216,32 @@ int w2v_dev_apply_rows(w2v_dev* h, float* rows, const uint8_t* codes, int32_t n,
   if (n < 0) return fail(W2V_ERR_ARG, "n < 0");
   if (set_device(h)) return W2V_ERR_HIP;
   const int64_t need = (int64_t)(n + 2) * h->pitch;
-  if (h->scratch_n < need) {
-    dfree(h->scratch_f); dfree(h->scratch_codes);
-    HIP_TRY(hipMalloc(&h->scratch_f, need * sizeof(float)));
-    HIP_TRY(hipMalloc(&h->scratch_codes, (size_t)(n > 64 ? n : 64)));
-    h->scratch_n = need;
+  if ((int64_t)h->scratch_f.size() < need) {
+    w2v::DevBuf<float> f;
+    w2v::DevBuf<uint8_t> c;
+    int rc;
+    if ((rc = f.alloc((size_t)need)) || (rc = c.alloc((size_t)(n > 64 ? n : 64)))) return rc;
+    h->scratch_f = std::move(f), h->scratch_codes = std::move(c);
   }
   const size_t d = (size_t)h->cfg.word_dim, dp = (size_t)h->pitch * sizeof(float);
-  float* dx = h->scratch_f;
-  float* dg = h->scratch_f + h->pitch;
-  float* dr = h->scratch_f + 2 * h->pitch;
-  HIP_TRY(hipMemsetAsync(h->scratch_f, 0, need * sizeof(float), h->stream));
-  HIP_TRY(hipMemcpyAsync(dx, x, d * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(dg, grad, d * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  float* dx = h->scratch_f.get();
+  float* dg = dx + h->pitch;
+  float* dr = dx + 2 * h->pitch;
+  W2V_HIP_TRY(hipMemsetAsync(dx, 0, need * sizeof(float), h->stream));
+  W2V_HIP_TRY(hipMemcpyAsync(dx, x, d * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  W2V_HIP_TRY(hipMemcpyAsync(dg, grad, d * sizeof(float), hipMemcpyHostToDevice, h->stream));
   if (n > 0) {
-    HIP_TRY(hipMemcpy2DAsync(dr, dp, rows, d * sizeof(float), d * sizeof(float), n, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->scratch_codes, codes, n, hipMemcpyHostToDevice, h->stream));
+    W2V_HIP_TRY(hipMemcpy2DAsync(dr, dp, rows, d * sizeof(float), d * sizeof(float), n, hipMemcpyHostToDevice, h->stream));
+    W2V_HIP_TRY(hipMemcpyAsync(h->scratch_codes.get(), codes, n, hipMemcpyHostToDevice, h->stream));
   }
   w2v::ApplyFn fn = apply_for(h);
-  hipLaunchKernelGGL(fn, dim3(1), dim3(64), 0, h->stream, dr, h->pitch, h->cfg.word_dim, dx, dg, h->scratch_codes,
+  hipLaunchKernelGGL(fn, dim3(1), dim3(64), 0, h->stream, dr, h->pitch, h->cfg.word_dim, dx, dg, h->scratch_codes.get(),
                      n, alpha, hs_form);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(grad, dg, d * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  W2V_HIP_TRY(hipGetLastError());
+  W2V_HIP_TRY(hipMemcpyAsync(grad, dg, d * sizeof(float), hipMemcpyDeviceToHost, h->stream));
   if (n > 0)
-    HIP_TRY(hipMemcpy2DAsync(rows, d * sizeof(float), dr, dp, d * sizeof(float), n, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+    W2V_HIP_TRY(hipMemcpy2DAsync(rows, d * sizeof(float), dr, dp, d * sizeof(float), n, hipMemcpyDeviceToHost, h->stream));
+  W2V_HIP_TRY(hipStreamSynchronize(h->stream));
   return W2V_OK;
 }
 

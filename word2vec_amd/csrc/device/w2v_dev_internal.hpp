@@ -16,6 +16,55 @@ namespace w2v {
 // Record `msg` as this thread's w2v_dev_last_error(); returns `code`.
 int set_error(int code, const std::string& msg);
 
+// Try a HIP call inside a function that returns a W2V_* code.
+#define W2V_HIP_TRY(expr)                                                                  \
+  do {                                                                                     \
+    hipError_t e_ = (expr);                                                                \
+    if (e_ != hipSuccess)                                                                  \
+      return w2v::set_error(W2V_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+  } while (0)
+
+// Device memory with one owner: move-only, freed by the destructor. An upload
+// fills local buffers and moves them into its handle after the last call that
+// can fail, so a failed call leaves the handle as it was and leaks nothing.
+template <class T>
+class DevBuf {
+ public:
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr, o.n_ = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) {
+      reset();
+      p_ = o.p_, n_ = o.n_;
+      o.p_ = nullptr, o.n_ = 0;
+    }
+    return *this;
+  }
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { reset(); }
+
+  T* get() const { return p_; }
+  size_t size() const { return n_; }  // elements
+  void reset() {
+    if (p_) (void)hipFree(p_);
+    p_ = nullptr, n_ = 0;
+  }
+  // n elements, uninitialised. The new block exists before the old one goes;
+  // a failure leaves the buffer as it was.
+  int alloc(size_t n) {
+    T* p = nullptr;
+    W2V_HIP_TRY(hipMalloc(&p, n * sizeof(T)));
+    reset();
+    p_ = p, n_ = n;
+    return W2V_OK;
+  }
+
+ private:
+  T* p_ = nullptr;
+  size_t n_ = 0;
+};
+
 struct DevInfo {
   int device;
   hipStream_t stream;

@@ -213,13 +213,13 @@ struct Member {
   hipEvent_t ready = nullptr;    // deltas extracted (train -> comm / replica 0)
   hipEvent_t done = nullptr;     // summed deltas ready (comm -> train)
   ncclComm_t nccl = nullptr;
-  float* mat[3] = {nullptr, nullptr, nullptr};  // W, C, synapses1 (device, pitch-padded rows)
-  float* P[3] = {nullptr, nullptr, nullptr};    // the shared model at the last exchange
-  float* D[3] = {nullptr, nullptr, nullptr};    // this replica's updates of the round being exchanged
-  float* A[3] = {nullptr, nullptr, nullptr};    // sum over replicas of D (same device: replica 0's only)
-  float* F[3] = {nullptr, nullptr, nullptr};    // rows this replica changed (ROW_AVERAGE)
-  float* FA[3] = {nullptr, nullptr, nullptr};   // contributors per row, summed (same device: replica 0's only)
-  float* WC[3] = {nullptr, nullptr, nullptr};   // W2V_GROUP_SPLIT / SATURATION: per-row divisor in [1, nranks]
+  float* mat[3] = {nullptr, nullptr, nullptr};  // W, C, synapses1 (the handle's, pitch-padded rows)
+  w2v::DevBuf<float> P[3];    // the shared model at the last exchange
+  w2v::DevBuf<float> D[3];    // this replica's updates of the round being exchanged
+  w2v::DevBuf<float> A[3];    // sum over replicas of D (same device: replica 0's only)
+  w2v::DevBuf<float> F[3];    // rows this replica changed (ROW_AVERAGE)
+  w2v::DevBuf<float> FA[3];   // contributors per row, summed (same device: replica 0's only)
+  w2v::DevBuf<float> WC[3];   // W2V_GROUP_SPLIT / SATURATION: per-row divisor in [1, nranks]
 };
 
 }  // namespace
@@ -255,50 +255,57 @@ struct w2v_group {
   } cur, pend;
   int64_t at(const Span& sp, int k) const { return sp.lo[k] * pitch; }    // element offset
   int64_t len(const Span& sp, int k) const { return sp.n[k] * pitch; }   // elements
+
+  ~w2v_group() {  // the members' buffers free themselves after this
+    for (Member& x : m) {
+      (void)hipSetDevice(x.device);
+      if (x.comm) (void)hipStreamSynchronize(x.comm);
+      if (x.train) (void)hipStreamSynchronize(x.train);
+      if (x.nccl) (void)ncclCommDestroy(x.nccl);
+      if (x.ready) (void)hipEventDestroy(x.ready);
+      if (x.done) (void)hipEventDestroy(x.done);
+      if (x.comm) (void)hipStreamDestroy(x.comm);
+    }
+  }
 };
 
 namespace {
 
-int fail_g(int code, const std::string& msg) { return w2v::set_error(code, msg); }
-
-#define HIP_G(expr)                                                                      \
-  do {                                                                                   \
-    hipError_t e_ = (expr);                                                              \
-    if (e_ != hipSuccess) return fail_g(W2V_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
 #define NCCL_G(expr)                                                                     \
   do {                                                                                   \
     ncclResult_t r_ = (expr);                                                            \
-    if (r_ != ncclSuccess) return fail_g(W2V_ERR_COMM, std::string(#expr) + ": " + ncclGetErrorString(r_)); \
+    if (r_ != ncclSuccess) return w2v::set_error(W2V_ERR_COMM, std::string(#expr) + ": " + ncclGetErrorString(r_)); \
   } while (0)
 
-void free_member(Member& x) {
-  (void)hipSetDevice(x.device);
-  if (x.comm) (void)hipStreamSynchronize(x.comm);
-  if (x.train) (void)hipStreamSynchronize(x.train);
-  for (int k = 0; k < 3; ++k) {
-    for (float** b : {&x.P[k], &x.D[k], &x.A[k], &x.F[k], &x.FA[k], &x.WC[k]}) {
-      if (*b) (void)hipFree(*b);
-      *b = nullptr;
-    }
+// A member's communication stream and events and, when the rounds exchange
+// anything, its buffers: P (the shared model: every replica starts from the
+// same weights), D, the row flags F and, with own_sum, the sums A and FA.
+int member_setup(const w2v_group* g, Member& x, bool own_sum) {
+  W2V_HIP_TRY(hipSetDevice(x.device));
+  W2V_HIP_TRY(hipStreamCreateWithFlags(&x.comm, hipStreamNonBlocking));
+  W2V_HIP_TRY(hipEventCreateWithFlags(&x.ready, hipEventDisableTiming));
+  W2V_HIP_TRY(hipEventCreateWithFlags(&x.done, hipEventDisableTiming));
+  for (int k = 0; k < 3 && g->exchange; ++k) {
+    if (!g->elems[k]) continue;
+    const size_t n = (size_t)g->elems[k];
+    const size_t fn = (size_t)((g->rows(k) + 3) & ~int64_t(3));  // rows, float4-padded
+    int rc;
+    if ((rc = x.P[k].alloc(n)) || (rc = x.D[k].alloc(n)) || (rc = x.F[k].alloc(fn))) return rc;
+    if (own_sum && ((rc = x.A[k].alloc(n)) || (rc = x.FA[k].alloc(fn)))) return rc;
+    W2V_HIP_TRY(hipMemsetAsync(x.F[k].get(), 0, fn * sizeof(float), x.train));
+    W2V_HIP_TRY(hipMemcpyAsync(x.P[k].get(), x.mat[k], n * sizeof(float), hipMemcpyDeviceToDevice, x.train));
   }
-  if (x.nccl) (void)ncclCommDestroy(x.nccl);
-  if (x.ready) (void)hipEventDestroy(x.ready);
-  if (x.done) (void)hipEventDestroy(x.done);
-  if (x.comm) (void)hipStreamDestroy(x.comm);
-  x.nccl = nullptr;
-  x.ready = x.done = nullptr;
-  x.comm = nullptr;
+  return W2V_OK;
 }
 
 // The summed deltas / per-row divisors of replica i's matrix k over span sp.
 const float* sum_of(const w2v_group* g, size_t i, int k, const w2v_group::Span& sp) {
-  return (g->local ? g->m[0].A[k] : g->m[i].A[k]) + g->at(sp, k);
+  return (g->local ? g->m[0] : g->m[i]).A[k].get() + g->at(sp, k);
 }
 const float* count_of(const w2v_group* g, size_t i, int k, const w2v_group::Span& sp) {
-  if (g->row_divisors()) return g->m[i].WC[k] + sp.lo[k];
+  if (g->row_divisors()) return g->m[i].WC[k].get() + sp.lo[k];
   if (!g->rows_counted()) return nullptr;
-  return (g->local ? g->m[0].FA[k] : g->m[i].FA[k]) + sp.lo[k];
+  return (g->local ? g->m[0] : g->m[i]).FA[k].get() + sp.lo[k];
 }
 
 // Fold a finished exchange into every replica (train streams): M += s A - D, P = M.
@@ -306,15 +313,15 @@ int fold_pending(w2v_group* g) {
   if (!g->pending) return W2V_OK;
   for (size_t i = 0; i < g->m.size(); ++i) {
     Member& x = g->m[i];
-    HIP_G(hipSetDevice(x.device));
-    HIP_G(hipStreamWaitEvent(x.train, g->local ? g->m[0].done : x.done, 0));
+    W2V_HIP_TRY(hipSetDevice(x.device));
+    W2V_HIP_TRY(hipStreamWaitEvent(x.train, g->local ? g->m[0].done : x.done, 0));
     const w2v_group::Span& sp = g->pend;
     for (int k = 0; k < 3; ++k)
       if (sp.n[k]) {
         const int64_t o = g->at(sp, k);
-        hipLaunchKernelGGL(w2v::replica_fold_kernel, dim3(kGrid), dim3(kBlock), 0, x.train, x.mat[k] + o, x.P[k] + o,
-                           x.D[k] + o, sum_of(g, i, k, sp), count_of(g, i, k, sp), g->scale(), g->pitch, g->len(sp, k));
-        HIP_G(hipGetLastError());
+        hipLaunchKernelGGL(w2v::replica_fold_kernel, dim3(kGrid), dim3(kBlock), 0, x.train, x.mat[k] + o,
+                           x.P[k].get() + o, x.D[k].get() + o, sum_of(g, i, k, sp), count_of(g, i, k, sp), g->scale(), g->pitch, g->len(sp, k));
+        W2V_HIP_TRY(hipGetLastError());
       }
   }
   g->pending = false;
@@ -329,36 +336,36 @@ int sum_deltas(w2v_group* g, bool on_comm) {
   if (g->local) {
     Member& x0 = g->m[0];
     hipStream_t s0 = on_comm ? x0.comm : x0.train;
-    HIP_G(hipSetDevice(x0.device));
-    for (auto& x : g->m) HIP_G(hipStreamWaitEvent(s0, x.ready, 0));
+    W2V_HIP_TRY(hipSetDevice(x0.device));
+    for (auto& x : g->m) W2V_HIP_TRY(hipStreamWaitEvent(s0, x.ready, 0));
     const w2v_group::Span& sp = g->cur;
     for (int k = 0; k < 3; ++k)
       if (sp.n[k]) {
         const int64_t o = g->at(sp, k), lo = sp.lo[k];
         w2v::PtrList pl{};
-        for (size_t i = 0; i < n; ++i) pl.p[i] = g->m[i].D[k] + o;
-        hipLaunchKernelGGL(w2v::replica_sum_kernel, dim3(kGrid), dim3(kBlock), 0, s0, pl, (int)n, x0.A[k] + o,
+        for (size_t i = 0; i < n; ++i) pl.p[i] = g->m[i].D[k].get() + o;
+        hipLaunchKernelGGL(w2v::replica_sum_kernel, dim3(kGrid), dim3(kBlock), 0, s0, pl, (int)n, x0.A[k].get() + o,
                            g->len(sp, k));
-        HIP_G(hipGetLastError());
+        W2V_HIP_TRY(hipGetLastError());
         if (g->rows_counted()) {
-          for (size_t i = 0; i < n; ++i) pl.p[i] = g->m[i].F[k] + lo;
-          hipLaunchKernelGGL(w2v::replica_sum1_kernel, dim3(kGrid), dim3(kBlock), 0, s0, pl, (int)n, x0.FA[k] + lo,
-                             sp.n[k]);
-          HIP_G(hipGetLastError());
+          for (size_t i = 0; i < n; ++i) pl.p[i] = g->m[i].F[k].get() + lo;
+          hipLaunchKernelGGL(w2v::replica_sum1_kernel, dim3(kGrid), dim3(kBlock), 0, s0, pl, (int)n,
+                             x0.FA[k].get() + lo, sp.n[k]);
+          W2V_HIP_TRY(hipGetLastError());
         }
         if (g->adaptive()) {
-          hipLaunchKernelGGL(w2v::row_coherence_kernel, dim3(kGrid), dim3(kBlock), 0, s0, x0.A[k] + o, g->pitch,
-                             sp.n[k], x0.FA[k] + lo);
-          HIP_G(hipGetLastError());
+          hipLaunchKernelGGL(w2v::row_coherence_kernel, dim3(kGrid), dim3(kBlock), 0, s0, x0.A[k].get() + o, g->pitch,
+                             sp.n[k], x0.FA[k].get() + lo);
+          W2V_HIP_TRY(hipGetLastError());
         }
       }
-    HIP_G(hipEventRecord(x0.done, s0));
+    W2V_HIP_TRY(hipEventRecord(x0.done, s0));
     return W2V_OK;
   }
   for (auto& x : g->m)
     if (on_comm) {
-      HIP_G(hipSetDevice(x.device));
-      HIP_G(hipStreamWaitEvent(x.comm, x.ready, 0));
+      W2V_HIP_TRY(hipSetDevice(x.device));
+      W2V_HIP_TRY(hipStreamWaitEvent(x.comm, x.ready, 0));
     }
   const w2v_group::Span& sp = g->cur;
   NCCL_G(ncclGroupStart());
@@ -367,29 +374,29 @@ int sum_deltas(w2v_group* g, bool on_comm) {
     for (int k = 0; k < 3; ++k)
       if (sp.n[k]) {
         const int64_t o = g->at(sp, k), lo = sp.lo[k];
-        ncclResult_t r = ncclAllReduce(x.D[k] + o, x.A[k] + o, (size_t)g->len(sp, k), ncclFloat32, ncclSum, x.nccl,
-                                       on_comm ? x.comm : x.train);
+        ncclResult_t r = ncclAllReduce(x.D[k].get() + o, x.A[k].get() + o, (size_t)g->len(sp, k), ncclFloat32, ncclSum,
+                                       x.nccl, on_comm ? x.comm : x.train);
         if (r == ncclSuccess && g->rows_counted())
-          r = ncclAllReduce(x.F[k] + lo, x.FA[k] + lo, (size_t)sp.n[k], ncclFloat32, ncclSum, x.nccl,
+          r = ncclAllReduce(x.F[k].get() + lo, x.FA[k].get() + lo, (size_t)sp.n[k], ncclFloat32, ncclSum, x.nccl,
                             on_comm ? x.comm : x.train);
         if (r != ncclSuccess) {
           (void)ncclGroupEnd();
-          return fail_g(W2V_ERR_COMM, std::string("ncclAllReduce: ") + ncclGetErrorString(r));
+          return w2v::set_error(W2V_ERR_COMM, std::string("ncclAllReduce: ") + ncclGetErrorString(r));
         }
       }
   }
   NCCL_G(ncclGroupEnd());
   for (auto& x : g->m) {
-    HIP_G(hipSetDevice(x.device));
+    W2V_HIP_TRY(hipSetDevice(x.device));
     hipStream_t st = on_comm ? x.comm : x.train;
     if (g->adaptive())
       for (int k = 0; k < 3; ++k)
         if (sp.n[k]) {
-          hipLaunchKernelGGL(w2v::row_coherence_kernel, dim3(kGrid), dim3(kBlock), 0, st, x.A[k] + g->at(sp, k),
-                             g->pitch, sp.n[k], x.FA[k] + sp.lo[k]);
-          HIP_G(hipGetLastError());
+          hipLaunchKernelGGL(w2v::row_coherence_kernel, dim3(kGrid), dim3(kBlock), 0, st,
+                             x.A[k].get() + g->at(sp, k), g->pitch, sp.n[k], x.FA[k].get() + sp.lo[k]);
+          W2V_HIP_TRY(hipGetLastError());
         }
-    HIP_G(hipEventRecord(x.done, st));
+    W2V_HIP_TRY(hipEventRecord(x.done, st));
   }
   return W2V_OK;
 }
@@ -407,31 +414,31 @@ int exchange(w2v_group* g) {
   if (fold)
     for (size_t i = 0; i < g->m.size(); ++i) {
       Member& x = g->m[i];
-      HIP_G(hipSetDevice(x.device));
-      HIP_G(hipStreamWaitEvent(x.train, g->local ? g->m[0].done : x.done, 0));
+      W2V_HIP_TRY(hipSetDevice(x.device));
+      W2V_HIP_TRY(hipStreamWaitEvent(x.train, g->local ? g->m[0].done : x.done, 0));
     }
   const w2v_group::Span& sp = g->cur;
   for (size_t i = 0; i < g->m.size(); ++i) {
     Member& x = g->m[i];
-    HIP_G(hipSetDevice(x.device));
+    W2V_HIP_TRY(hipSetDevice(x.device));
     for (int k = 0; k < 3; ++k)
       if (sp.n[k]) {
         const int64_t o = g->at(sp, k), lo = sp.lo[k];
-        hipLaunchKernelGGL(w2v::replica_delta_kernel, dim3(kGrid), dim3(kBlock), 0, x.train, x.mat[k] + o, x.P[k] + o,
-                           x.D[k] + o, fold ? sum_of(g, i, k, sp) : nullptr, fold ? count_of(g, i, k, sp) : nullptr,
+        hipLaunchKernelGGL(w2v::replica_delta_kernel, dim3(kGrid), dim3(kBlock), 0, x.train, x.mat[k] + o,
+                           x.P[k].get() + o, x.D[k].get() + o, fold ? sum_of(g, i, k, sp) : nullptr, fold ? count_of(g, i, k, sp) : nullptr,
                            g->scale(), fold ? 1 : 0, g->pitch, g->len(sp, k));
-        HIP_G(hipGetLastError());
+        W2V_HIP_TRY(hipGetLastError());
         if (g->adaptive()) {
-          hipLaunchKernelGGL(w2v::row_norm2_kernel, dim3(kGrid), dim3(kBlock), 0, x.train, x.D[k] + o, g->pitch,
-                             sp.n[k], x.F[k] + lo);
-          HIP_G(hipGetLastError());
+          hipLaunchKernelGGL(w2v::row_norm2_kernel, dim3(kGrid), dim3(kBlock), 0, x.train, x.D[k].get() + o,
+                             g->pitch, sp.n[k], x.F[k].get() + lo);
+          W2V_HIP_TRY(hipGetLastError());
         } else if (g->rows_counted()) {
-          hipLaunchKernelGGL(w2v::row_touch_kernel, dim3(kGrid), dim3(kBlock), 0, x.train, x.D[k] + o, g->pitch,
-                             sp.n[k], x.F[k] + lo);
-          HIP_G(hipGetLastError());
+          hipLaunchKernelGGL(w2v::row_touch_kernel, dim3(kGrid), dim3(kBlock), 0, x.train, x.D[k].get() + o,
+                             g->pitch, sp.n[k], x.F[k].get() + lo);
+          W2V_HIP_TRY(hipGetLastError());
         }
       }
-    HIP_G(hipEventRecord(x.ready, x.train));
+    W2V_HIP_TRY(hipEventRecord(x.ready, x.train));
   }
   g->pending = false;
   if (int rc = sum_deltas(g, g->overlap)) return rc;
@@ -446,7 +453,7 @@ int exchange(w2v_group* g) {
 extern "C" {
 
 int w2v_group_unique_id(uint8_t* id) {
-  if (!id) return fail_g(W2V_ERR_ARG, "w2v_group_unique_id: null argument");
+  if (!id) return w2v::set_error(W2V_ERR_ARG, "w2v_group_unique_id: null argument");
   static_assert(sizeof(ncclUniqueId) == W2V_GROUP_ID_BYTES, "ncclUniqueId size");
   ncclUniqueId u;
   NCCL_G(ncclGetUniqueId(&u));
@@ -457,15 +464,15 @@ int w2v_group_unique_id(uint8_t* id) {
 int w2v_group_create(w2v_dev** members, int32_t n, const uint8_t* unique_id, int32_t nranks, int32_t first_rank,
                      w2v_group** out) {
   w2v::Range range_("w2v_group_create");
-  if (!members || !out || n < 1) return fail_g(W2V_ERR_ARG, "w2v_group_create: need >= 1 member handle");
+  if (!members || !out || n < 1) return w2v::set_error(W2V_ERR_ARG, "w2v_group_create: need >= 1 member handle");
   *out = nullptr;
-  if (n > w2v::kGroupMaxLocal) return fail_g(W2V_ERR_UNSUPPORTED, "w2v_group_create: at most 16 replicas per process");
+  if (n > w2v::kGroupMaxLocal) return w2v::set_error(W2V_ERR_UNSUPPORTED, "w2v_group_create: at most 16 replicas per process");
   if (!unique_id) {
     nranks = n;
     first_rank = 0;
   }
   if (nranks < n || first_rank < 0 || first_rank + n > nranks)
-    return fail_g(W2V_ERR_ARG, "w2v_group_create: ranks [first_rank, first_rank + n) must lie in [0, nranks)");
+    return w2v::set_error(W2V_ERR_ARG, "w2v_group_create: ranks [first_rank, first_rank + n) must lie in [0, nranks)");
   w2v_group* g = new w2v_group();
   g->nranks = nranks;
   for (int i = 0; i < n; ++i) {
@@ -474,8 +481,8 @@ int w2v_group_create(w2v_dev** members, int32_t n, const uint8_t* unique_id, int
     x.h = h;
     int64_t pitch = 0;
     if (!h || w2v_dev_model_layout(h, &x.mat[0], &x.mat[1], &x.mat[2], &pitch) != W2V_OK) {
-      w2v_group_destroy(g);
-      return fail_g(W2V_ERR_STATE, "w2v_group_create: every member needs its vocab and model resident");
+      delete g;
+      return w2v::set_error(W2V_ERR_STATE, "w2v_group_create: every member needs its vocab and model resident");
     }
     w2v::DevInfo info = w2v::dev_info(h);
     x.device = info.device;
@@ -486,39 +493,21 @@ int w2v_group_create(w2v_dev** members, int32_t n, const uint8_t* unique_id, int
     for (int k = 0; k < 3; ++k) {
       if (i == 0) g->elems[k] = e[k];
       else if (g->elems[k] != e[k]) {
-        w2v_group_destroy(g);
-        return fail_g(W2V_ERR_ARG, "w2v_group_create: members must hold models of the same shape");
+        delete g;
+        return w2v::set_error(W2V_ERR_ARG, "w2v_group_create: members must hold models of the same shape");
       }
     }
-    g->m.push_back(x);
+    g->m.push_back(std::move(x));
   }
   bool same = true;
   for (auto& x : g->m) same = same && x.device == g->m[0].device;
   g->local = n > 1 && same && !unique_id;
   g->exchange = nranks > 1 || unique_id != nullptr;
-  for (size_t i = 0; i < g->m.size(); ++i) {
-    Member& x = g->m[i];
-    bool ok = hipSetDevice(x.device) == hipSuccess &&
-              hipStreamCreateWithFlags(&x.comm, hipStreamNonBlocking) == hipSuccess &&
-              hipEventCreateWithFlags(&x.ready, hipEventDisableTiming) == hipSuccess &&
-              hipEventCreateWithFlags(&x.done, hipEventDisableTiming) == hipSuccess;
-    // P (the shared model: every replica starts from the same weights), D, A
-    for (int k = 0; k < 3 && ok && g->exchange; ++k) {
-      if (!g->elems[k]) continue;
-      const size_t bytes = (size_t)g->elems[k] * sizeof(float);
-      const size_t fbytes = (size_t)((g->elems[k] / g->pitch + 3) & ~int64_t(3)) * sizeof(float);  // rows, float4-padded
-      const bool own_sum = !(g->local && i > 0);
-      ok = hipMalloc(&x.P[k], bytes) == hipSuccess && hipMalloc(&x.D[k], bytes) == hipSuccess &&
-           (!own_sum || hipMalloc(&x.A[k], bytes) == hipSuccess) && hipMalloc(&x.F[k], fbytes) == hipSuccess &&
-           hipMemsetAsync(x.F[k], 0, fbytes, x.train) == hipSuccess &&
-           (!own_sum || hipMalloc(&x.FA[k], fbytes) == hipSuccess) &&
-           hipMemcpyAsync(x.P[k], x.mat[k], bytes, hipMemcpyDeviceToDevice, x.train) == hipSuccess;
+  for (size_t i = 0; i < g->m.size(); ++i)
+    if (int rc = member_setup(g, g->m[i], !(g->local && i > 0))) {
+      delete g;  // what the member got so far goes with the group
+      return rc;
     }
-    if (!ok) {
-      w2v_group_destroy(g);
-      return fail_g(W2V_ERR_HIP, "w2v_group_create: stream / event / exchange buffer setup failed (out of memory?)");
-    }
-  }
   if (!g->local && g->exchange) {
     ncclResult_t r = ncclSuccess;
     if (!unique_id) {
@@ -540,39 +529,35 @@ int w2v_group_create(w2v_dev** members, int32_t n, const uint8_t* unique_id, int
       if (r == ncclSuccess) r = r2;
     }
     if (r != ncclSuccess) {
-      w2v_group_destroy(g);
-      return fail_g(W2V_ERR_COMM, std::string("w2v_group_create: RCCL communicator: ") + ncclGetErrorString(r));
+      delete g;
+      return w2v::set_error(W2V_ERR_COMM, std::string("w2v_group_create: RCCL communicator: ") + ncclGetErrorString(r));
     }
   }
   for (auto& x : g->m)  // the shared-model copies P are taken before the caller touches the replicas again
     if (hipSetDevice(x.device) != hipSuccess || hipStreamSynchronize(x.train) != hipSuccess) {
-      w2v_group_destroy(g);
-      return fail_g(W2V_ERR_HIP, "w2v_group_create: synchronising the replicas failed");
+      delete g;
+      return w2v::set_error(W2V_ERR_HIP, "w2v_group_create: synchronising the replicas failed");
     }
   for (auto& x : g->m) w2v::set_replicas(x.h, nranks);
   *out = g;
   return W2V_OK;
 }
 
-void w2v_group_destroy(w2v_group* g) {
-  if (!g) return;
-  for (auto& x : g->m) free_member(x);
-  delete g;
-}
+void w2v_group_destroy(w2v_group* g) { delete g; }
 
 int w2v_group_set_overlap(w2v_group* g, int32_t on) {
-  if (!g) return fail_g(W2V_ERR_ARG, "null group");
-  if (g->pending) return fail_g(W2V_ERR_STATE, "w2v_group_set_overlap: an exchange is in flight (w2v_group_finish first)");
+  if (!g) return w2v::set_error(W2V_ERR_ARG, "null group");
+  if (g->pending) return w2v::set_error(W2V_ERR_STATE, "w2v_group_set_overlap: an exchange is in flight (w2v_group_finish first)");
   g->overlap = on != 0;
   return W2V_OK;
 }
 
 int w2v_group_set_mode(w2v_group* g, int32_t mode) {
-  if (!g) return fail_g(W2V_ERR_ARG, "null group");
+  if (!g) return w2v::set_error(W2V_ERR_ARG, "null group");
   if (mode != W2V_GROUP_SUM && mode != W2V_GROUP_AVERAGE && mode != W2V_GROUP_ROW_AVERAGE &&
       mode != W2V_GROUP_ADAPTIVE)
-    return fail_g(W2V_ERR_ARG, "bad group mode (W2V_GROUP_SPLIT is set by w2v_group_set_split)");
-  if (g->pending) return fail_g(W2V_ERR_STATE, "w2v_group_set_mode: an exchange is in flight (w2v_group_finish first)");
+    return w2v::set_error(W2V_ERR_ARG, "bad group mode (W2V_GROUP_SPLIT is set by w2v_group_set_split)");
+  if (g->pending) return w2v::set_error(W2V_ERR_STATE, "w2v_group_set_mode: an exchange is in flight (w2v_group_finish first)");
   g->mode = mode;
   return W2V_OK;
 }
@@ -586,22 +571,24 @@ namespace {
 // tokens_per_round raw tokens.
 template <class F>
 int set_row_divisors(w2v_group* g, int64_t tokens_per_round, int32_t mode, F divisor, const char* what) {
-  if (g->pending) return fail_g(W2V_ERR_STATE, std::string(what) + ": an exchange is in flight (w2v_group_finish first)");
+  if (g->pending) return w2v::set_error(W2V_ERR_STATE, std::string(what) + ": an exchange is in flight (w2v_group_finish first)");
   std::vector<float> wc[3];
   for (int k = 0; k < 3; ++k) {
     if (!g->elems[k]) continue;
     std::vector<double> rate;
     if (!w2v::row_update_rates(g->m[0].h, k, rate) || (int64_t)rate.size() != g->rows(k))
-      return fail_g(W2V_ERR_STATE, std::string(what) + ": the replicas need their vocab and corpus statistics uploaded");
+      return w2v::set_error(W2V_ERR_STATE, std::string(what) + ": the replicas need their vocab and corpus statistics uploaded");
     wc[k].resize(rate.size());
     for (size_t r = 0; r < rate.size(); ++r) wc[k][r] = divisor(rate[r] * (double)tokens_per_round);
   }
   for (auto& x : g->m) {
-    HIP_G(hipSetDevice(x.device));
+    W2V_HIP_TRY(hipSetDevice(x.device));
     for (int k = 0; k < 3; ++k) {
       if (!g->elems[k]) continue;
-      if (!x.WC[k]) HIP_G(hipMalloc(&x.WC[k], wc[k].size() * sizeof(float)));
-      HIP_G(hipMemcpy(x.WC[k], wc[k].data(), wc[k].size() * sizeof(float), hipMemcpyHostToDevice));
+      w2v::DevBuf<float> d;
+      if (int rc = d.alloc(wc[k].size())) return rc;
+      W2V_HIP_TRY(hipMemcpy(d.get(), wc[k].data(), wc[k].size() * sizeof(float), hipMemcpyHostToDevice));
+      x.WC[k] = std::move(d);
     }
   }
   int64_t avg = 0;
@@ -617,9 +604,9 @@ extern "C" {
 
 int w2v_group_set_split(w2v_group* g, int64_t tokens_per_round, float saturated_updates) {
   w2v::Range range_("w2v_group_set_split");
-  if (!g) return fail_g(W2V_ERR_ARG, "null group");
+  if (!g) return w2v::set_error(W2V_ERR_ARG, "null group");
   if (tokens_per_round < 1 || !(saturated_updates >= 0.0f))
-    return fail_g(W2V_ERR_ARG, "w2v_group_set_split: tokens_per_round >= 1 and saturated_updates >= 0");
+    return w2v::set_error(W2V_ERR_ARG, "w2v_group_set_split: tokens_per_round >= 1 and saturated_updates >= 0");
   const float R = (float)g->nranks;
   return set_row_divisors(g, tokens_per_round, W2V_GROUP_SPLIT,
                           [&](double u) { return u >= (double)saturated_updates ? R : 1.0f; }, "w2v_group_set_split");
@@ -636,9 +623,9 @@ int w2v_group_set_split(w2v_group* g, int64_t tokens_per_round, float saturated_
 // such moves overshoots R-fold, which is GD past its stability bound for R > 2).
 int w2v_group_set_saturation(w2v_group* g, int64_t tokens_per_round, float beta) {
   w2v::Range range_("w2v_group_set_saturation");
-  if (!g) return fail_g(W2V_ERR_ARG, "null group");
+  if (!g) return w2v::set_error(W2V_ERR_ARG, "null group");
   if (tokens_per_round < 1 || !(beta > 0.0f && beta < 1.0f))
-    return fail_g(W2V_ERR_ARG, "w2v_group_set_saturation: tokens_per_round >= 1 and 0 < beta < 1");
+    return w2v::set_error(W2V_ERR_ARG, "w2v_group_set_saturation: tokens_per_round >= 1 and 0 < beta < 1");
   const double R = (double)g->nranks, lb = std::log1p(-(double)beta);
   return set_row_divisors(g, tokens_per_round, W2V_GROUP_SATURATION, [&](double u) {
     const double a = -std::expm1(u * lb), b = -std::expm1(R * u * lb);
@@ -649,7 +636,7 @@ int w2v_group_set_saturation(w2v_group* g, int64_t tokens_per_round, float beta)
 
 int w2v_group_average_async(w2v_group* g) {
   w2v::Range range_("w2v_group_average_async");
-  if (!g) return fail_g(W2V_ERR_ARG, "null group");
+  if (!g) return w2v::set_error(W2V_ERR_ARG, "null group");
   for (int k = 0; k < 3; ++k) {
     g->cur.lo[k] = 0;
     g->cur.n[k] = g->rows(k);
@@ -659,8 +646,8 @@ int w2v_group_average_async(w2v_group* g) {
 
 int w2v_group_average_rows_async(w2v_group* g, int64_t rows) {
   w2v::Range range_("w2v_group_average_rows_async");
-  if (!g) return fail_g(W2V_ERR_ARG, "null group");
-  if (rows < 0) return fail_g(W2V_ERR_ARG, "w2v_group_average_rows_async: rows must be >= 0");
+  if (!g) return w2v::set_error(W2V_ERR_ARG, "null group");
+  if (rows < 0) return w2v::set_error(W2V_ERR_ARG, "w2v_group_average_rows_async: rows must be >= 0");
   for (int k = 0; k < 3; ++k) {  // W / C: the first rows (the most frequent words); synapses1: the nodes nearest the root
     const int64_t R = g->rows(k), n = rows == 0 ? R : std::min(rows, R);
     g->cur.lo[k] = k == 2 ? R - n : 0;
@@ -671,37 +658,37 @@ int w2v_group_average_rows_async(w2v_group* g, int64_t rows) {
 
 int w2v_group_finish(w2v_group* g) {
   w2v::Range range_("w2v_group_finish");
-  if (!g) return fail_g(W2V_ERR_ARG, "null group");
+  if (!g) return w2v::set_error(W2V_ERR_ARG, "null group");
   if (int rc = fold_pending(g)) return rc;
   for (auto& x : g->m) {
-    HIP_G(hipSetDevice(x.device));
-    HIP_G(hipStreamSynchronize(x.train));
-    HIP_G(hipStreamSynchronize(x.comm));
+    W2V_HIP_TRY(hipSetDevice(x.device));
+    W2V_HIP_TRY(hipStreamSynchronize(x.train));
+    W2V_HIP_TRY(hipStreamSynchronize(x.comm));
   }
   return W2V_OK;
 }
 
 int w2v_group_row_divisors(w2v_group* g, int32_t which, float* out, int64_t n) {
-  if (!g || !out) return fail_g(W2V_ERR_ARG, "null argument");
-  if (which < 0 || which > 2 || !g->elems[which]) return fail_g(W2V_ERR_ARG, "no such matrix in the group");
-  if (n != g->rows(which)) return fail_g(W2V_ERR_ARG, "n must be the matrix's row count");
+  if (!g || !out) return w2v::set_error(W2V_ERR_ARG, "null argument");
+  if (which < 0 || which > 2 || !g->elems[which]) return w2v::set_error(W2V_ERR_ARG, "no such matrix in the group");
+  if (n != g->rows(which)) return w2v::set_error(W2V_ERR_ARG, "n must be the matrix's row count");
   if (!g->row_divisors()) {
     std::fill(out, out + n, 1.0f);
     return W2V_OK;
   }
-  HIP_G(hipSetDevice(g->m[0].device));
-  HIP_G(hipMemcpy(out, g->m[0].WC[which], (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+  W2V_HIP_TRY(hipSetDevice(g->m[0].device));
+  W2V_HIP_TRY(hipMemcpy(out, g->m[0].WC[which].get(), (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
   return W2V_OK;
 }
 
 int w2v_group_split_rows(w2v_group* g, int64_t* rows) {
-  if (!g || !rows) return fail_g(W2V_ERR_ARG, "null argument");
+  if (!g || !rows) return w2v::set_error(W2V_ERR_ARG, "null argument");
   *rows = g->row_divisors() ? g->split_rows : 0;
   return W2V_OK;
 }
 
 int w2v_group_info(w2v_group* g, int32_t* nranks, int32_t* local, int32_t* overlap, int64_t* rounds) {
-  if (!g) return fail_g(W2V_ERR_ARG, "null group");
+  if (!g) return w2v::set_error(W2V_ERR_ARG, "null group");
   if (nranks) *nranks = g->nranks;
   if (local) *local = g->local ? 1 : 0;
   if (overlap) *overlap = g->overlap ? 1 : 0;

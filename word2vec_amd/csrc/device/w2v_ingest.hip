@@ -359,61 +359,65 @@ inline dim3 grid_for(int64_t n) {
 
 using namespace w2v::ingest;
 
+using w2v::DevBuf;
+
+// The hash table's memory; the kernels take its view.
+struct TableBuf {
+  DevBuf<uint64_t> key, h2;
+  DevBuf<unsigned long long> first, count;
+  DevBuf<uint32_t> len;
+  int64_t cap() const { return (int64_t)key.size(); }
+  Table view() const { return Table{key.get(), h2.get(), first.get(), count.get(), len.get(), (uint64_t)cap() - 1}; }
+};
+
+// The chunk work buffers, sized together (ensure_work).
+struct Work {
+  DevBuf<unsigned char> buf;  // one chunk (the file is not resident), and a byte more
+  DevBuf<int64_t> tile;       // per-4 KiB-tile start counts, then positions
+  DevBuf<int64_t> starts;
+  DevBuf<uint32_t> nl_after;
+  DevBuf<uint32_t> slot;
+  DevBuf<int64_t> line_of;
+  DevBuf<int32_t> tok_id;
+  DevBuf<int32_t> kept;
+  DevBuf<int32_t> kpos;
+  DevBuf<int64_t> n_sel;
+  DevBuf<unsigned char> temp;  // scratch of the selects and scans
+};
+
 struct w2v_ingest {
   int device = 0;
   int format = W2V_INGEST_LINES;
   int64_t chunk = (int64_t)1 << 30;
   int64_t resident_max = kResidentMax;
   hipStream_t stream = nullptr;
-  // hash table
-  int64_t cap = 0;
-  Table tab{};
-  unsigned long long* ctr = nullptr;  // [0] used slots, [1] probe failures, [2] mismatches
+  TableBuf tab;
+  DevBuf<unsigned long long> ctr;  // [0] used slots, [1] probe failures, [2] mismatches
   // pass 1 results
   bool counted = false;
   int64_t n_bytes = 0, raw_tokens = 0, n_sentences = 0, n_words = 0;
-  int64_t* order = nullptr;  // device: the used slots in order of first occurrence
+  DevBuf<int64_t> order;  // the used slots in order of first occurrence
   std::vector<int64_t> word_count;  // host: pass-1 counts in that order
   // pass 2 results
   bool mapped = false;
-  int32_t* ids = nullptr;
+  DevBuf<int32_t> ids;
   int64_t n_ids = 0;
-  int64_t* offsets = nullptr;  // n_sentences + 1
+  DevBuf<int64_t> offsets;  // n_sentences + 1
   std::vector<int64_t> hist;   // host: tokens per vocab id
-  // chunk work buffers
-  unsigned char* buf = nullptr;   // one chunk (the file is not resident)
-  unsigned char* file = nullptr;  // the whole file in HBM between pass 1 and pass 2 (<= kResidentMax)
-  int64_t file_n = -1;
+  DevBuf<unsigned char> file;  // the whole file in HBM between pass 1 and pass 2 (<= kResidentMax)
   const unsigned char* cur = nullptr;  // device bytes of the current chunk
-  int64_t* tile = nullptr;             // per-4 KiB-tile start counts, then positions
-  int64_t* starts = nullptr;
-  uint32_t* nl_after = nullptr;
-  uint32_t* slot = nullptr;
-  int64_t* line_of = nullptr;
-  int32_t* tok_id = nullptr;
-  int32_t* kept = nullptr;
-  int32_t* kpos = nullptr;
-  int64_t* n_sel = nullptr;
-  void* temp = nullptr;
-  size_t temp_bytes = 0;
-  int64_t work_cap = 0;  // bytes the work buffers hold
+  Work w;
+
+  ~w2v_ingest() {  // the buffers free themselves after this
+    (void)hipSetDevice(device);
+    if (stream) {
+      (void)hipStreamSynchronize(stream);
+      (void)hipStreamDestroy(stream);
+    }
+  }
 };
 
 namespace {
-
-int fail_i(int code, const std::string& m) { return w2v::set_error(code, m); }
-
-#define HIP_I(expr)                                                                                       \
-  do {                                                                                                    \
-    hipError_t e_ = (expr);                                                                               \
-    if (e_ != hipSuccess) return fail_i(W2V_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-template <class T>
-void dfree(T*& p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
 
 bool host_space(char c) { return c == ' ' || c == '\t' || c == '\n' || c == '\v' || c == '\f' || c == '\r'; }
 
@@ -430,20 +434,18 @@ std::vector<std::pair<int64_t, int64_t>> chunks(const char* p, int64_t n, int64_
   return r;
 }
 
-void free_table(Table& t) {
-  dfree(t.key); dfree(t.h2); dfree(t.first); dfree(t.count); dfree(t.len);
-}
-
-int alloc_table(Table& t, int64_t cap, hipStream_t s) {
-  HIP_I(hipMalloc(&t.key, cap * sizeof(uint64_t)));
-  HIP_I(hipMalloc(&t.h2, cap * sizeof(uint64_t)));
-  HIP_I(hipMalloc(&t.first, cap * sizeof(unsigned long long)));
-  HIP_I(hipMalloc(&t.count, cap * sizeof(unsigned long long)));
-  HIP_I(hipMalloc(&t.len, cap * sizeof(uint32_t)));
-  HIP_I(hipMemsetAsync(t.key, 0, cap * sizeof(uint64_t), s));
-  HIP_I(hipMemsetAsync(t.first, 0xFF, cap * sizeof(unsigned long long), s));
-  HIP_I(hipMemsetAsync(t.count, 0, cap * sizeof(unsigned long long), s));
-  t.mask = (uint64_t)cap - 1;
+// An empty table of `cap` slots (a power of two) into `out`.
+int alloc_table(TableBuf& out, int64_t cap, hipStream_t s) {
+  TableBuf t;
+  const size_t n = (size_t)cap;
+  int rc;
+  if ((rc = t.key.alloc(n)) || (rc = t.h2.alloc(n)) || (rc = t.first.alloc(n)) || (rc = t.count.alloc(n)) ||
+      (rc = t.len.alloc(n)))
+    return rc;
+  W2V_HIP_TRY(hipMemsetAsync(t.key.get(), 0, n * sizeof(uint64_t), s));
+  W2V_HIP_TRY(hipMemsetAsync(t.first.get(), 0xFF, n * sizeof(unsigned long long), s));
+  W2V_HIP_TRY(hipMemsetAsync(t.count.get(), 0, n * sizeof(unsigned long long), s));
+  out = std::move(t);
   return W2V_OK;
 }
 
@@ -451,24 +453,20 @@ constexpr int64_t kMaxCap = (int64_t)1 << 30;
 
 // Double the table until it holds `need` words at most half full.
 int grow(w2v_ingest* g, int64_t need) {
-  int64_t cap = g->cap * 2;
+  int64_t cap = g->tab.cap() * 2;
   while (cap < 2 * need) cap <<= 1;
-  if (cap > kMaxCap) return fail_i(W2V_ERR_UNSUPPORTED, "w2v_ingest_count: more than 2^29 distinct words");
-  Table nt{};
-  if (int rc = alloc_table(nt, cap, g->stream)) {
-    free_table(nt);
-    return rc;
-  }
-  HIP_I(hipMemsetAsync(g->ctr + 1, 0, sizeof(unsigned long long), g->stream));
-  hipLaunchKernelGGL(rehash_kernel, grid_for(g->cap), dim3(kBlock), 0, g->stream, g->tab, g->cap, nt, g->ctr + 1);
-  HIP_I(hipGetLastError());
+  if (cap > kMaxCap) return w2v::set_error(W2V_ERR_UNSUPPORTED, "w2v_ingest_count: more than 2^29 distinct words");
+  TableBuf nt;
+  if (int rc = alloc_table(nt, cap, g->stream)) return rc;
+  W2V_HIP_TRY(hipMemsetAsync(g->ctr.get() + 1, 0, sizeof(unsigned long long), g->stream));
+  hipLaunchKernelGGL(rehash_kernel, grid_for(g->tab.cap()), dim3(kBlock), 0, g->stream, g->tab.view(), g->tab.cap(),
+                     nt.view(), g->ctr.get() + 1);
+  W2V_HIP_TRY(hipGetLastError());
   unsigned long long f = 0;
-  HIP_I(hipMemcpyAsync(&f, g->ctr + 1, sizeof(f), hipMemcpyDeviceToHost, g->stream));
-  HIP_I(hipStreamSynchronize(g->stream));
-  free_table(g->tab);
-  g->tab = nt;
-  g->cap = cap;
-  if (f) return fail_i(W2V_ERR_STATE, "w2v_ingest_count: rehash lost words");
+  W2V_HIP_TRY(hipMemcpyAsync(&f, g->ctr.get() + 1, sizeof(f), hipMemcpyDeviceToHost, g->stream));
+  W2V_HIP_TRY(hipStreamSynchronize(g->stream));
+  g->tab = std::move(nt);
+  if (f) return w2v::set_error(W2V_ERR_STATE, "w2v_ingest_count: rehash lost words");
   return W2V_OK;
 }
 
@@ -478,76 +476,70 @@ int grow(w2v_ingest* g, int64_t need) {
 // kMaxCap) and the words (<= 2^29) all fit the (int) casts below.
 int ensure_work(w2v_ingest* g, int64_t bytes) {
   if (bytes < 0 || bytes > (int64_t)INT32_MAX - 64)
-    return fail_i(W2V_ERR_UNSUPPORTED, "w2v_ingest: a chunk must be < 2^31 - 64 bytes (hipcub int counts)");
-  if (g->work_cap >= bytes) return W2V_OK;
-  dfree(g->buf); dfree(g->tile); dfree(g->starts); dfree(g->nl_after); dfree(g->slot); dfree(g->line_of);
-  dfree(g->tok_id); dfree(g->kept); dfree(g->kpos); dfree(g->n_sel);
-  if (g->temp) (void)hipFree(g->temp);
-  g->temp = nullptr;
-  g->work_cap = 0;
-  const int64_t max_tok = bytes / 2 + 1;  // a token and its separator take >= 2 bytes
-  HIP_I(hipMalloc(&g->buf, bytes + 1));
-  const int64_t n_tiles = bytes / kTileBytes + 2;
-  HIP_I(hipMalloc(&g->tile, n_tiles * sizeof(int64_t)));
-  HIP_I(hipMalloc(&g->starts, max_tok * sizeof(int64_t)));
-  HIP_I(hipMalloc(&g->nl_after, max_tok * sizeof(uint32_t)));
-  HIP_I(hipMalloc(&g->slot, max_tok * sizeof(uint32_t)));
-  HIP_I(hipMalloc(&g->line_of, max_tok * sizeof(int64_t)));
-  HIP_I(hipMalloc(&g->tok_id, max_tok * sizeof(int32_t)));
-  HIP_I(hipMalloc(&g->kept, max_tok * sizeof(int32_t)));
-  HIP_I(hipMalloc(&g->kpos, max_tok * sizeof(int32_t)));
-  HIP_I(hipMalloc(&g->n_sel, sizeof(int64_t)));
+    return w2v::set_error(W2V_ERR_UNSUPPORTED, "w2v_ingest: a chunk must be < 2^31 - 64 bytes (hipcub int counts)");
+  if ((int64_t)g->w.buf.size() > bytes) return W2V_OK;
+  Work w;
+  const size_t max_tok = (size_t)bytes / 2 + 1;  // a token and its separator take >= 2 bytes
+  const size_t n_tiles = (size_t)bytes / kTileBytes + 2;
+  int rc;
+  if ((rc = w.buf.alloc((size_t)bytes + 1)) || (rc = w.tile.alloc(n_tiles)) || (rc = w.starts.alloc(max_tok)) ||
+      (rc = w.nl_after.alloc(max_tok)) || (rc = w.slot.alloc(max_tok)) || (rc = w.line_of.alloc(max_tok)) ||
+      (rc = w.tok_id.alloc(max_tok)) || (rc = w.kept.alloc(max_tok)) || (rc = w.kpos.alloc(max_tok)) ||
+      (rc = w.n_sel.alloc(1)))
+    return rc;
   // scratch for the selects and scans at the largest size
   size_t t1 = 0, t2 = 0, t3 = 0, t4 = 0;
-  const int nk = (int)std::min<int64_t>(max_tok, INT32_MAX);
-  HIP_I(hipcub::DeviceScan::ExclusiveSum(nullptr, t1, g->tile, g->tile, (int)n_tiles));
-  HIP_I(hipcub::DeviceScan::ExclusiveSum(nullptr, t2, g->nl_after, g->line_of, nk));
-  HIP_I(hipcub::DeviceSelect::If(nullptr, t3, g->tok_id, g->tok_id, g->n_sel, nk, NotNegative()));
-  HIP_I(hipcub::DeviceScan::ExclusiveSum(nullptr, t4, g->kept, g->kpos, nk));
-  g->temp_bytes = std::max({t1, t2, t3, t4});
-  HIP_I(hipMalloc(&g->temp, g->temp_bytes));
-  g->work_cap = bytes;
+  const int nk = (int)std::min<size_t>(max_tok, INT32_MAX);
+  W2V_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, t1, w.tile.get(), w.tile.get(), (int)n_tiles));
+  W2V_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, t2, w.nl_after.get(), w.line_of.get(), nk));
+  W2V_HIP_TRY(hipcub::DeviceSelect::If(nullptr, t3, w.tok_id.get(), w.tok_id.get(), w.n_sel.get(), nk, NotNegative()));
+  W2V_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, t4, w.kept.get(), w.kpos.get(), nk));
+  if ((rc = w.temp.alloc(std::max({t1, t2, t3, t4})))) return rc;
+  g->w = std::move(w);
   return W2V_OK;
 }
 
 // The chunk's bytes on the device (copied unless the file is resident), and
 // its token starts; returns the token count in *nt.
 int tokenize(w2v_ingest* g, const char* data, int64_t off, int64_t n, int64_t* nt) {
-  if (g->file) {
-    g->cur = g->file + off;
+  Work& w = g->w;
+  if (g->file.get()) {
+    g->cur = g->file.get() + off;
   } else {
-    HIP_I(hipMemcpyAsync(g->buf, data + off, n, hipMemcpyHostToDevice, g->stream));
-    g->cur = g->buf;
+    W2V_HIP_TRY(hipMemcpyAsync(w.buf.get(), data + off, n, hipMemcpyHostToDevice, g->stream));
+    g->cur = w.buf.get();
   }
   const int64_t n_tiles = (n + kTileBytes - 1) / kTileBytes;
   if (n_tiles == 0) {
     *nt = 0;
     return W2V_OK;
   }
-  HIP_I(hipMemsetAsync(g->tile + n_tiles, 0, sizeof(int64_t), g->stream));
-  hipLaunchKernelGGL(tile_count_kernel, dim3((unsigned)n_tiles), dim3(256), 0, g->stream, g->cur, n, g->tile);
-  HIP_I(hipGetLastError());
-  size_t tb = g->temp_bytes;
-  HIP_I(hipcub::DeviceScan::ExclusiveSum(g->temp, tb, g->tile, g->tile, (int)n_tiles + 1, g->stream));
-  hipLaunchKernelGGL(tile_write_kernel, dim3((unsigned)n_tiles), dim3(256), 0, g->stream, g->cur, n, g->tile,
-                     g->starts);
-  HIP_I(hipGetLastError());
-  HIP_I(hipMemcpyAsync(nt, g->tile + n_tiles, sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
-  HIP_I(hipStreamSynchronize(g->stream));
+  int64_t* tile = w.tile.get();
+  W2V_HIP_TRY(hipMemsetAsync(tile + n_tiles, 0, sizeof(int64_t), g->stream));
+  hipLaunchKernelGGL(tile_count_kernel, dim3((unsigned)n_tiles), dim3(256), 0, g->stream, g->cur, n, tile);
+  W2V_HIP_TRY(hipGetLastError());
+  size_t tb = w.temp.size();
+  W2V_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(w.temp.get(), tb, tile, tile, (int)n_tiles + 1, g->stream));
+  hipLaunchKernelGGL(tile_write_kernel, dim3((unsigned)n_tiles), dim3(256), 0, g->stream, g->cur, n, tile,
+                     w.starts.get());
+  W2V_HIP_TRY(hipGetLastError());
+  W2V_HIP_TRY(hipMemcpyAsync(nt, tile + n_tiles, sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
+  W2V_HIP_TRY(hipStreamSynchronize(g->stream));
   return W2V_OK;
 }
 
 // Line index of each token of the chunk (line_base + newlines before it in the
 // chunk); returns the newline count after the chunk's last token in *after.
 int lines_of(w2v_ingest* g, int64_t nt, int64_t line_base, int64_t* last_line, int64_t* after) {
-  size_t tb = g->temp_bytes;
-  HIP_I(hipcub::DeviceScan::ExclusiveSum(g->temp, tb, g->nl_after, g->line_of, (int)nt, g->stream));
-  hipLaunchKernelGGL(add_base_kernel, grid_for(nt), dim3(kBlock), 0, g->stream, g->line_of, nt, line_base);
-  HIP_I(hipGetLastError());
+  Work& w = g->w;
+  size_t tb = w.temp.size();
+  W2V_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(w.temp.get(), tb, w.nl_after.get(), w.line_of.get(), (int)nt, g->stream));
+  hipLaunchKernelGGL(add_base_kernel, grid_for(nt), dim3(kBlock), 0, g->stream, w.line_of.get(), nt, line_base);
+  W2V_HIP_TRY(hipGetLastError());
   uint32_t last_nl = 0;
-  HIP_I(hipMemcpyAsync(last_line, g->line_of + nt - 1, sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
-  HIP_I(hipMemcpyAsync(&last_nl, g->nl_after + nt - 1, sizeof(uint32_t), hipMemcpyDeviceToHost, g->stream));
-  HIP_I(hipStreamSynchronize(g->stream));
+  W2V_HIP_TRY(hipMemcpyAsync(last_line, w.line_of.get() + nt - 1, sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
+  W2V_HIP_TRY(hipMemcpyAsync(&last_nl, w.nl_after.get() + nt - 1, sizeof(uint32_t), hipMemcpyDeviceToHost, g->stream));
+  W2V_HIP_TRY(hipStreamSynchronize(g->stream));
   *after = last_nl;
   return W2V_OK;
 }
@@ -561,46 +553,59 @@ int64_t leading_newlines(const char* p, int64_t n) {
 
 int64_t chunk_size_limit(const w2v_ingest* g) { return std::min<int64_t>(g->chunk, (int64_t)INT32_MAX - 64); }
 
-// The used slots sorted by first occurrence -> g->order; their counts -> g->word_count.
+// The used slots sorted by first occurrence -> g->order.
 int order_words(w2v_ingest* g, int64_t n_words) {
-  dfree(g->order);
-  HIP_I(hipMalloc(&g->order, std::max<int64_t>(n_words, 1) * sizeof(int64_t)));
-  if (n_words == 0) return W2V_OK;
-  int64_t* slots = nullptr;
-  unsigned long long *firsts = nullptr, *firsts_sorted = nullptr;
-  void* tmp = nullptr;
-  auto cleanup = [&] {
-    dfree(slots); dfree(firsts); dfree(firsts_sorted);
-    if (tmp) (void)hipFree(tmp);
-  };
-  int rc = [&]() -> int {
-    HIP_I(hipMalloc(&slots, n_words * sizeof(int64_t)));
-    HIP_I(hipMalloc(&firsts, n_words * sizeof(unsigned long long)));
-    HIP_I(hipMalloc(&firsts_sorted, n_words * sizeof(unsigned long long)));
+  DevBuf<int64_t> order, slots;
+  DevBuf<unsigned long long> firsts, firsts_sorted;
+  DevBuf<unsigned char> tmp;
+  int rc;
+  if ((rc = order.alloc((size_t)std::max<int64_t>(n_words, 1)))) return rc;
+  if (n_words > 0) {
+    const size_t m = (size_t)n_words;
+    const int cap = (int)g->tab.cap();
+    int64_t* n_sel = g->w.n_sel.get();
+    if ((rc = slots.alloc(m)) || (rc = firsts.alloc(m)) || (rc = firsts_sorted.alloc(m))) return rc;
     hipcub::CountingInputIterator<int64_t> it(0);
+    const UsedSlot used{g->tab.key.get()};
     size_t t1 = 0, t2 = 0;
-    HIP_I(hipcub::DeviceSelect::If(nullptr, t1, it, slots, g->n_sel, (int)g->cap, UsedSlot{g->tab.key}, g->stream));
-    HIP_I(hipcub::DeviceRadixSort::SortPairs(nullptr, t2, firsts, firsts_sorted, slots, g->order, (int)n_words, 0, 64,
-                                             g->stream));
-    const size_t tb = std::max<size_t>(std::max(t1, t2), 1);
-    HIP_I(hipMalloc(&tmp, tb));
-    size_t t = tb;
-    HIP_I(hipcub::DeviceSelect::If(tmp, t, it, slots, g->n_sel, (int)g->cap, UsedSlot{g->tab.key}, g->stream));
+    W2V_HIP_TRY(hipcub::DeviceSelect::If(nullptr, t1, it, slots.get(), n_sel, cap, used, g->stream));
+    W2V_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, t2, firsts.get(), firsts_sorted.get(), slots.get(),
+                                                   order.get(), (int)n_words, 0, 64, g->stream));
+    if ((rc = tmp.alloc(std::max<size_t>(std::max(t1, t2), 1)))) return rc;
+    size_t t = tmp.size();
+    W2V_HIP_TRY(hipcub::DeviceSelect::If(tmp.get(), t, it, slots.get(), n_sel, cap, used, g->stream));
     int64_t sel = 0;
-    HIP_I(hipMemcpyAsync(&sel, g->n_sel, sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
-    HIP_I(hipStreamSynchronize(g->stream));
-    if (sel != n_words) return fail_i(W2V_ERR_STATE, "w2v_ingest_count: used-slot count mismatch");
-    hipLaunchKernelGGL(gather_first_kernel, grid_for(n_words), dim3(kBlock), 0, g->stream, slots, n_words,
-                       g->tab.first, firsts);
-    HIP_I(hipGetLastError());
-    t = tb;
-    HIP_I(hipcub::DeviceRadixSort::SortPairs(tmp, t, firsts, firsts_sorted, slots, g->order, (int)n_words, 0, 64,
-                                             g->stream));
-    HIP_I(hipStreamSynchronize(g->stream));
-    return W2V_OK;
-  }();
-  cleanup();
-  return rc;
+    W2V_HIP_TRY(hipMemcpyAsync(&sel, n_sel, sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
+    W2V_HIP_TRY(hipStreamSynchronize(g->stream));
+    if (sel != n_words) return w2v::set_error(W2V_ERR_STATE, "w2v_ingest_count: used-slot count mismatch");
+    hipLaunchKernelGGL(gather_first_kernel, grid_for(n_words), dim3(kBlock), 0, g->stream, slots.get(), n_words,
+                       g->tab.first.get(), firsts.get());
+    W2V_HIP_TRY(hipGetLastError());
+    t = tmp.size();
+    W2V_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.get(), t, firsts.get(), firsts_sorted.get(), slots.get(),
+                                                   order.get(), (int)n_words, 0, 64, g->stream));
+    W2V_HIP_TRY(hipStreamSynchronize(g->stream));
+  }
+  g->order = std::move(order);
+  return W2V_OK;
+}
+
+// The first m words in g->order's order: first byte offset, length and count,
+// each to the host array given (nullptr: not wanted).
+int gather_words(w2v_ingest* g, int64_t m, int64_t* first_offset, int32_t* length, int64_t* count) {
+  DevBuf<int64_t> d_first, d_count;
+  DevBuf<int32_t> d_len;
+  int rc;
+  if ((rc = d_first.alloc((size_t)m)) || (rc = d_len.alloc((size_t)m)) || (rc = d_count.alloc((size_t)m))) return rc;
+  hipLaunchKernelGGL(gather_words_kernel, grid_for(m), dim3(kBlock), 0, g->stream, g->order.get(), m, g->tab.view(),
+                     d_first.get(), d_len.get(), d_count.get());
+  W2V_HIP_TRY(hipGetLastError());
+  if (first_offset)
+    W2V_HIP_TRY(hipMemcpyAsync(first_offset, d_first.get(), m * sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
+  if (length) W2V_HIP_TRY(hipMemcpyAsync(length, d_len.get(), m * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
+  if (count) W2V_HIP_TRY(hipMemcpyAsync(count, d_count.get(), m * sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
+  W2V_HIP_TRY(hipStreamSynchronize(g->stream));
+  return W2V_OK;
 }
 
 }  // namespace
@@ -608,10 +613,10 @@ int order_words(w2v_ingest* g, int64_t n_words) {
 extern "C" {
 
 int w2v_ingest_create(int32_t device, int32_t format, int64_t chunk_bytes, w2v_ingest** out) {
-  if (!out) return fail_i(W2V_ERR_ARG, "w2v_ingest_create: null argument");
+  if (!out) return w2v::set_error(W2V_ERR_ARG, "w2v_ingest_create: null argument");
   *out = nullptr;
-  if (format != W2V_INGEST_LINES && format != W2V_INGEST_TEXT8) return fail_i(W2V_ERR_ARG, "bad ingest format");
-  if (chunk_bytes < 0) return fail_i(W2V_ERR_ARG, "chunk_bytes must be >= 0");
+  if (format != W2V_INGEST_LINES && format != W2V_INGEST_TEXT8) return w2v::set_error(W2V_ERR_ARG, "bad ingest format");
+  if (chunk_bytes < 0) return w2v::set_error(W2V_ERR_ARG, "chunk_bytes must be >= 0");
   w2v_ingest* g = new w2v_ingest();
   g->format = format;
   if (chunk_bytes > 0) g->chunk = std::max<int64_t>(chunk_bytes, 1 << 12);
@@ -620,68 +625,57 @@ int w2v_ingest_create(int32_t device, int32_t format, int64_t chunk_bytes, w2v_i
   else e = hipGetDevice(&g->device);
   if (e == hipSuccess) e = hipSetDevice(g->device);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipMalloc(&g->ctr, 3 * sizeof(unsigned long long));
   if (e != hipSuccess) {
-    w2v_ingest_destroy(g);
-    return fail_i(W2V_ERR_HIP, std::string("w2v_ingest_create: ") + hipGetErrorString(e));
+    delete g;
+    return w2v::set_error(W2V_ERR_HIP, std::string("w2v_ingest_create: ") + hipGetErrorString(e));
+  }
+  if (int rc = g->ctr.alloc(3)) {
+    delete g;
+    return rc;
   }
   *out = g;
   return W2V_OK;
 }
 
-void w2v_ingest_destroy(w2v_ingest* g) {
-  if (!g) return;
-  (void)hipSetDevice(g->device);
-  if (g->stream) (void)hipStreamSynchronize(g->stream);
-  free_table(g->tab);
-  dfree(g->ctr); dfree(g->order); dfree(g->ids); dfree(g->offsets); dfree(g->file);
-  dfree(g->buf); dfree(g->tile); dfree(g->starts); dfree(g->nl_after); dfree(g->slot); dfree(g->line_of);
-  dfree(g->tok_id); dfree(g->kept); dfree(g->kpos); dfree(g->n_sel);
-  if (g->temp) (void)hipFree(g->temp);
-  if (g->stream) (void)hipStreamDestroy(g->stream);
-  delete g;
-}
+void w2v_ingest_destroy(w2v_ingest* g) { delete g; }
 
 int w2v_ingest_set_resident(w2v_ingest* g, int64_t max_bytes) {
-  if (!g) return fail_i(W2V_ERR_ARG, "null ingest");
+  if (!g) return w2v::set_error(W2V_ERR_ARG, "null ingest");
   g->resident_max = max_bytes < 0 ? kResidentMax : max_bytes;
   return W2V_OK;
 }
 
 int w2v_ingest_count(w2v_ingest* g, const char* data, int64_t n) {
-  if (!g || (n > 0 && !data) || n < 0) return fail_i(W2V_ERR_ARG, "w2v_ingest_count: bad argument");
+  if (!g || (n > 0 && !data) || n < 0) return w2v::set_error(W2V_ERR_ARG, "w2v_ingest_count: bad argument");
   w2v::Range range_("w2v_ingest_count");
-  HIP_I(hipSetDevice(g->device));
+  W2V_HIP_TRY(hipSetDevice(g->device));
   g->counted = g->mapped = false;
   const bool lines = g->format == W2V_INGEST_LINES;
   const auto cs = chunks(data, n, chunk_size_limit(g), lines);
   int64_t biggest = 0;
   for (auto& c : cs) biggest = std::max(biggest, c.second - c.first);
-  if (biggest > (int64_t)INT32_MAX - 64) return fail_i(W2V_ERR_UNSUPPORTED, "w2v_ingest_count: a line longer than 2 GiB");
+  if (biggest > (int64_t)INT32_MAX - 64) return w2v::set_error(W2V_ERR_UNSUPPORTED, "w2v_ingest_count: a line longer than 2 GiB");
   if (int rc = ensure_work(g, std::max<int64_t>(biggest, 1))) return rc;
   // a file that fits the residency budget crosses PCIe once: pass 2 reads this copy
-  dfree(g->file);
-  g->file_n = -1;
+  g->file.reset();
   // ... and only while it leaves at least half of the device's free memory to
   // the work buffers, the table and whatever trains next on this device
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
   if (n > 0 && n <= g->resident_max && (uint64_t)n <= (uint64_t)free_b / 2) {
-    if (hipMalloc(&g->file, n) == hipSuccess) {
-      HIP_I(hipMemcpyAsync(g->file, data, n, hipMemcpyHostToDevice, g->stream));
-      g->file_n = n;
+    DevBuf<unsigned char> file;
+    if (file.alloc((size_t)n) == W2V_OK) {
+      W2V_HIP_TRY(hipMemcpyAsync(file.get(), data, n, hipMemcpyHostToDevice, g->stream));
+      g->file = std::move(file);
     } else {
       (void)hipGetLastError();  // no room: stream the chunks in both passes instead
-      g->file = nullptr;
     }
   }
   // the table starts at 2^16..2^24 slots and doubles whenever it is half full
-  free_table(g->tab);
   int64_t cap = (int64_t)1 << 16;
   while (cap < std::min<int64_t>(n / 64, (int64_t)1 << 24)) cap <<= 1;
   if (int rc = alloc_table(g->tab, cap, g->stream)) return rc;
-  g->cap = cap;
-  HIP_I(hipMemsetAsync(g->ctr, 0, 3 * sizeof(unsigned long long), g->stream));
+  W2V_HIP_TRY(hipMemsetAsync(g->ctr.get(), 0, 3 * sizeof(unsigned long long), g->stream));
   int64_t raw = 0, newlines = 0;
   for (auto& c : cs) {
     const int64_t len = c.second - c.first;
@@ -690,18 +684,19 @@ int w2v_ingest_count(w2v_ingest* g, const char* data, int64_t n) {
     newlines += leading_newlines(data + c.first, len);
     if (nt > 0) {
       for (;;) {  // insert until no token failed to find a slot and the table is at most half full
-        HIP_I(hipMemsetAsync(g->ctr + 1, 0, sizeof(unsigned long long), g->stream));
-        hipLaunchKernelGGL(insert_kernel, grid_for(nt), dim3(kBlock), 0, g->stream, g->cur, len, g->starts, nt,
-                           c.first, g->tab, g->slot, g->nl_after, g->ctr, g->ctr + 1);
-        HIP_I(hipGetLastError());
+        W2V_HIP_TRY(hipMemsetAsync(g->ctr.get() + 1, 0, sizeof(unsigned long long), g->stream));
+        hipLaunchKernelGGL(insert_kernel, grid_for(nt), dim3(kBlock), 0, g->stream, g->cur, len, g->w.starts.get(), nt,
+                           c.first, g->tab.view(), g->w.slot.get(), g->w.nl_after.get(), g->ctr.get(), g->ctr.get() + 1);
+        W2V_HIP_TRY(hipGetLastError());
         unsigned long long cnt[2] = {0, 0};
-        HIP_I(hipMemcpyAsync(cnt, g->ctr, sizeof(cnt), hipMemcpyDeviceToHost, g->stream));
-        HIP_I(hipStreamSynchronize(g->stream));
-        if (cnt[1] == 0 && (int64_t)cnt[0] * 2 <= g->cap) break;
+        W2V_HIP_TRY(hipMemcpyAsync(cnt, g->ctr.get(), sizeof(cnt), hipMemcpyDeviceToHost, g->stream));
+        W2V_HIP_TRY(hipStreamSynchronize(g->stream));
+        if (cnt[1] == 0 && (int64_t)cnt[0] * 2 <= g->tab.cap()) break;
         if (int rc = grow(g, (int64_t)cnt[0] + (int64_t)cnt[1])) return rc;
       }
-      hipLaunchKernelGGL(count_kernel, grid_for(nt / 16), dim3(kBlock), 0, g->stream, g->slot, nt, g->tab.count);
-      HIP_I(hipGetLastError());
+      hipLaunchKernelGGL(count_kernel, grid_for(nt / 16), dim3(kBlock), 0, g->stream, g->w.slot.get(), nt,
+                         g->tab.count.get());
+      W2V_HIP_TRY(hipGetLastError());
       int64_t last_line = 0, after = 0;
       if (int rc = lines_of(g, nt, 0, &last_line, &after)) return rc;
       newlines += last_line + after;
@@ -709,25 +704,12 @@ int w2v_ingest_count(w2v_ingest* g, const char* data, int64_t n) {
     raw += nt;
   }
   unsigned long long used = 0;
-  HIP_I(hipMemcpy(&used, g->ctr, sizeof(used), hipMemcpyDeviceToHost));
+  W2V_HIP_TRY(hipMemcpy(&used, g->ctr.get(), sizeof(used), hipMemcpyDeviceToHost));
   if (int rc = order_words(g, (int64_t)used)) return rc;
   g->n_words = (int64_t)used;
   g->word_count.assign((size_t)used, 0);
-  if (used > 0) {
-    int64_t *d_first = nullptr, *d_count = nullptr;
-    int32_t* d_len = nullptr;
-    HIP_I(hipMalloc(&d_first, used * sizeof(int64_t)));
-    HIP_I(hipMalloc(&d_len, used * sizeof(int32_t)));
-    HIP_I(hipMalloc(&d_count, used * sizeof(int64_t)));
-    hipLaunchKernelGGL(gather_words_kernel, grid_for((int64_t)used), dim3(kBlock), 0, g->stream, g->order,
-                       (int64_t)used, g->tab, d_first, d_len, d_count);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(g->word_count.data(), d_count, used * sizeof(int64_t), hipMemcpyDeviceToHost,
-                                            g->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
-    dfree(d_first); dfree(d_len); dfree(d_count);
-    if (e != hipSuccess) return fail_i(W2V_ERR_HIP, std::string("w2v_ingest_count: ") + hipGetErrorString(e));
-  }
+  if (used > 0)
+    if (int rc = gather_words(g, (int64_t)used, nullptr, nullptr, g->word_count.data())) return rc;
   g->n_bytes = n;
   g->raw_tokens = raw;
   // sentences: lines (getline: a final unterminated line counts when it holds bytes) or 1000-token cuts
@@ -738,8 +720,8 @@ int w2v_ingest_count(w2v_ingest* g, const char* data, int64_t n) {
 }
 
 int w2v_ingest_summary(w2v_ingest* g, int64_t* n_words, int64_t* raw_tokens, int64_t* n_sentences) {
-  if (!g) return fail_i(W2V_ERR_ARG, "null ingest");
-  if (!g->counted) return fail_i(W2V_ERR_STATE, "w2v_ingest_count first");
+  if (!g) return w2v::set_error(W2V_ERR_ARG, "null ingest");
+  if (!g->counted) return w2v::set_error(W2V_ERR_STATE, "w2v_ingest_count first");
   if (n_words) *n_words = g->n_words;
   if (raw_tokens) *raw_tokens = g->raw_tokens;
   if (n_sentences) *n_sentences = g->n_sentences;
@@ -747,121 +729,105 @@ int w2v_ingest_summary(w2v_ingest* g, int64_t* n_words, int64_t* raw_tokens, int
 }
 
 int w2v_ingest_words(w2v_ingest* g, int64_t* first_offset, int32_t* length, int64_t* count) {
-  if (!g) return fail_i(W2V_ERR_ARG, "null ingest");
-  if (!g->counted) return fail_i(W2V_ERR_STATE, "w2v_ingest_count first");
+  if (!g) return w2v::set_error(W2V_ERR_ARG, "null ingest");
+  if (!g->counted) return w2v::set_error(W2V_ERR_STATE, "w2v_ingest_count first");
   const int64_t m = g->n_words;
   if (m == 0) return W2V_OK;
-  HIP_I(hipSetDevice(g->device));
-  int64_t *d_first = nullptr, *d_count = nullptr;
-  int32_t* d_len = nullptr;
-  auto cleanup = [&] { dfree(d_first); dfree(d_len); dfree(d_count); };
-  int rc = [&]() -> int {
-    HIP_I(hipMalloc(&d_first, m * sizeof(int64_t)));
-    HIP_I(hipMalloc(&d_len, m * sizeof(int32_t)));
-    HIP_I(hipMalloc(&d_count, m * sizeof(int64_t)));
-    hipLaunchKernelGGL(gather_words_kernel, grid_for(m), dim3(kBlock), 0, g->stream, g->order, m, g->tab, d_first,
-                       d_len, d_count);
-    HIP_I(hipGetLastError());
-    if (first_offset) HIP_I(hipMemcpyAsync(first_offset, d_first, m * sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
-    if (length) HIP_I(hipMemcpyAsync(length, d_len, m * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
-    if (count) HIP_I(hipMemcpyAsync(count, d_count, m * sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
-    HIP_I(hipStreamSynchronize(g->stream));
-    return W2V_OK;
-  }();
-  cleanup();
-  return rc;
+  W2V_HIP_TRY(hipSetDevice(g->device));
+  return gather_words(g, m, first_offset, length, count);
 }
 
 int w2v_ingest_map(w2v_ingest* g, const char* data, int64_t n, const int32_t* vocab_index, int64_t n_words) {
-  if (!g || (n > 0 && !data) || (n_words > 0 && !vocab_index)) return fail_i(W2V_ERR_ARG, "w2v_ingest_map: null argument");
-  if (!g->counted) return fail_i(W2V_ERR_STATE, "w2v_ingest_count first");
-  if (n != g->n_bytes || n_words != g->n_words) return fail_i(W2V_ERR_ARG, "w2v_ingest_map: not the counted corpus");
+  if (!g || (n > 0 && !data) || (n_words > 0 && !vocab_index)) return w2v::set_error(W2V_ERR_ARG, "w2v_ingest_map: null argument");
+  if (!g->counted) return w2v::set_error(W2V_ERR_STATE, "w2v_ingest_count first");
+  if (n != g->n_bytes || n_words != g->n_words) return w2v::set_error(W2V_ERR_ARG, "w2v_ingest_map: not the counted corpus");
   w2v::Range range_("w2v_ingest_map");
-  HIP_I(hipSetDevice(g->device));
+  W2V_HIP_TRY(hipSetDevice(g->device));
   g->mapped = false;
   int32_t vmax = -1;
   for (int64_t k = 0; k < n_words; ++k) {
-    if (vocab_index[k] < -1) return fail_i(W2V_ERR_ARG, "vocab_index entries must be >= -1");
+    if (vocab_index[k] < -1) return w2v::set_error(W2V_ERR_ARG, "vocab_index entries must be >= -1");
     vmax = std::max(vmax, vocab_index[k]);
   }
   // per-id token histogram: every occurrence of an in-vocab word is kept
-  g->hist.assign((size_t)vmax + 1, 0);
+  std::vector<int64_t> hist((size_t)vmax + 1, 0);
   for (int64_t k = 0; k < n_words; ++k)
-    if (vocab_index[k] >= 0) g->hist[(size_t)vocab_index[k]] += g->word_count[(size_t)k];
+    if (vocab_index[k] >= 0) hist[(size_t)vocab_index[k]] += g->word_count[(size_t)k];
   // slot -> vocab index
-  int32_t *d_slot = nullptr, *d_vidx = nullptr;
-  auto cleanup = [&] { dfree(d_slot); dfree(d_vidx); };
-  int rc = [&]() -> int {
-    HIP_I(hipMalloc(&d_slot, g->cap * sizeof(int32_t)));
-    HIP_I(hipMemsetAsync(d_slot, 0xFF, g->cap * sizeof(int32_t), g->stream));
-    if (n_words > 0) {
-      HIP_I(hipMalloc(&d_vidx, n_words * sizeof(int32_t)));
-      HIP_I(hipMemcpyAsync(d_vidx, vocab_index, n_words * sizeof(int32_t), hipMemcpyHostToDevice, g->stream));
-      hipLaunchKernelGGL(scatter_ids_kernel, grid_for(n_words), dim3(kBlock), 0, g->stream, g->order, d_vidx, n_words,
-                         d_slot);
-      HIP_I(hipGetLastError());
+  DevBuf<int32_t> d_slot, d_vidx, ids;
+  DevBuf<int64_t> offsets;
+  const int64_t cap = g->tab.cap();
+  int rc;
+  if ((rc = d_slot.alloc((size_t)cap))) return rc;
+  W2V_HIP_TRY(hipMemsetAsync(d_slot.get(), 0xFF, cap * sizeof(int32_t), g->stream));
+  if (n_words > 0) {
+    if ((rc = d_vidx.alloc((size_t)n_words))) return rc;
+    W2V_HIP_TRY(hipMemcpyAsync(d_vidx.get(), vocab_index, n_words * sizeof(int32_t), hipMemcpyHostToDevice, g->stream));
+    hipLaunchKernelGGL(scatter_ids_kernel, grid_for(n_words), dim3(kBlock), 0, g->stream, g->order.get(), d_vidx.get(),
+                       n_words, d_slot.get());
+    W2V_HIP_TRY(hipGetLastError());
+  }
+  if ((rc = ids.alloc((size_t)std::max<int64_t>(g->raw_tokens, 1))) || (rc = offsets.alloc((size_t)g->n_sentences + 1)))
+    return rc;
+  W2V_HIP_TRY(hipMemsetAsync(offsets.get(), 0, (g->n_sentences + 1) * sizeof(int64_t), g->stream));
+  unsigned long long* mismatch = g->ctr.get() + 2;
+  W2V_HIP_TRY(hipMemsetAsync(mismatch, 0, sizeof(unsigned long long), g->stream));
+  const bool lines = g->format == W2V_INGEST_LINES;
+  const auto cs = chunks(data, n, chunk_size_limit(g), lines);
+  Work& w = g->w;
+  int64_t raw = 0, kept = 0, line_base = 0, prev_line = -1;
+  for (auto& c : cs) {
+    const int64_t len = c.second - c.first;
+    int64_t nt = 0;
+    if ((rc = tokenize(g, data, c.first, len, &nt))) return rc;
+    line_base += leading_newlines(data + c.first, len);
+    if (nt > 0) {
+      hipLaunchKernelGGL(map_kernel, grid_for(nt), dim3(kBlock), 0, g->stream, g->cur, len, w.starts.get(), nt,
+                         g->tab.view(), d_slot.get(), w.tok_id.get(), w.kept.get(), w.nl_after.get(), mismatch);
+      W2V_HIP_TRY(hipGetLastError());
+      int64_t last_line = 0, after = 0;
+      if ((rc = lines_of(g, nt, line_base, &last_line, &after))) return rc;
+      size_t tb = w.temp.size();
+      W2V_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(w.temp.get(), tb, w.kept.get(), w.kpos.get(), (int)nt, g->stream));
+      hipLaunchKernelGGL(boundary_kernel, grid_for(nt), dim3(kBlock), 0, g->stream, w.kpos.get(), w.line_of.get(), nt,
+                         raw, kept, prev_line, lines ? 0 : 1, offsets.get());
+      W2V_HIP_TRY(hipGetLastError());
+      // append the chunk's in-vocab ids
+      tb = w.temp.size();
+      W2V_HIP_TRY(hipcub::DeviceSelect::If(w.temp.get(), tb, w.tok_id.get(), ids.get() + kept, w.n_sel.get(), (int)nt,
+                                           NotNegative(), g->stream));
+      int64_t sel = 0;
+      W2V_HIP_TRY(hipMemcpyAsync(&sel, w.n_sel.get(), sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
+      W2V_HIP_TRY(hipStreamSynchronize(g->stream));
+      kept += sel;
+      prev_line = last_line;
+      line_base = last_line + after;
     }
-    dfree(g->ids); dfree(g->offsets);
-    HIP_I(hipMalloc(&g->ids, std::max<int64_t>(g->raw_tokens, 1) * sizeof(int32_t)));
-    HIP_I(hipMalloc(&g->offsets, (g->n_sentences + 1) * sizeof(int64_t)));
-    HIP_I(hipMemsetAsync(g->offsets, 0, (g->n_sentences + 1) * sizeof(int64_t), g->stream));
-    HIP_I(hipMemsetAsync(g->ctr + 2, 0, sizeof(unsigned long long), g->stream));
-    const bool lines = g->format == W2V_INGEST_LINES;
-    const auto cs = chunks(data, n, chunk_size_limit(g), lines);
-    int64_t raw = 0, kept = 0, line_base = 0, prev_line = -1;
-    for (auto& c : cs) {
-      const int64_t len = c.second - c.first;
-      int64_t nt = 0;
-      if (int rc2 = tokenize(g, data, c.first, len, &nt)) return rc2;
-      line_base += leading_newlines(data + c.first, len);
-      if (nt > 0) {
-        hipLaunchKernelGGL(map_kernel, grid_for(nt), dim3(kBlock), 0, g->stream, g->cur, len, g->starts, nt, g->tab,
-                           d_slot, g->tok_id, g->kept, g->nl_after, g->ctr + 2);
-        HIP_I(hipGetLastError());
-        int64_t last_line = 0, after = 0;
-        if (int rc2 = lines_of(g, nt, line_base, &last_line, &after)) return rc2;
-        size_t tb = g->temp_bytes;
-        HIP_I(hipcub::DeviceScan::ExclusiveSum(g->temp, tb, g->kept, g->kpos, (int)nt, g->stream));
-        hipLaunchKernelGGL(boundary_kernel, grid_for(nt), dim3(kBlock), 0, g->stream, g->kpos, g->line_of, nt, raw, kept,
-                           prev_line, lines ? 0 : 1, g->offsets);
-        HIP_I(hipGetLastError());
-        // append the chunk's in-vocab ids
-        tb = g->temp_bytes;
-        HIP_I(hipcub::DeviceSelect::If(g->temp, tb, g->tok_id, g->ids + kept, g->n_sel, (int)nt, NotNegative(),
-                                       g->stream));
-        int64_t sel = 0;
-        HIP_I(hipMemcpyAsync(&sel, g->n_sel, sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
-        HIP_I(hipStreamSynchronize(g->stream));
-        kept += sel;
-        prev_line = last_line;
-        line_base = last_line + after;
-      }
-      raw += nt;
-    }
-    if (raw != g->raw_tokens) return fail_i(W2V_ERR_STATE, "w2v_ingest_map: token count differs from pass 1");
-    // the sentences after the last token's (lines: trailing empty lines) and the end
-    const int64_t tail = lines ? prev_line + 1 : g->n_sentences;
-    hipLaunchKernelGGL(fill_kernel, grid_for(g->n_sentences + 1 - tail), dim3(kBlock), 0, g->stream, g->offsets, tail,
-                       g->n_sentences + 1, kept);
-    HIP_I(hipGetLastError());
-    unsigned long long mism = 0;
-    HIP_I(hipMemcpyAsync(&mism, g->ctr + 2, sizeof(mism), hipMemcpyDeviceToHost, g->stream));
-    HIP_I(hipStreamSynchronize(g->stream));
-    if (mism > 0)
-      return fail_i(W2V_ERR_UNSUPPORTED, "w2v_ingest_map: " + std::to_string(mism) +
-                                             " tokens matched a word by the first hash but not the second "
-                                             "(a collision) or were not counted: the bytes differ from pass 1");
-    g->n_ids = kept;
-    return W2V_OK;
-  }();
-  cleanup();
-  if (rc == W2V_OK) g->mapped = true;
-  return rc;
+    raw += nt;
+  }
+  if (raw != g->raw_tokens) return w2v::set_error(W2V_ERR_STATE, "w2v_ingest_map: token count differs from pass 1");
+  // the sentences after the last token's (lines: trailing empty lines) and the end
+  const int64_t tail = lines ? prev_line + 1 : g->n_sentences;
+  hipLaunchKernelGGL(fill_kernel, grid_for(g->n_sentences + 1 - tail), dim3(kBlock), 0, g->stream, offsets.get(), tail,
+                     g->n_sentences + 1, kept);
+  W2V_HIP_TRY(hipGetLastError());
+  unsigned long long mism = 0;
+  W2V_HIP_TRY(hipMemcpyAsync(&mism, mismatch, sizeof(mism), hipMemcpyDeviceToHost, g->stream));
+  W2V_HIP_TRY(hipStreamSynchronize(g->stream));
+  if (mism > 0)
+    return w2v::set_error(W2V_ERR_UNSUPPORTED, "w2v_ingest_map: " + std::to_string(mism) +
+                                                   " tokens matched a word by the first hash but not the second "
+                                                   "(a collision) or were not counted: the bytes differ from pass 1");
+  g->ids = std::move(ids), g->offsets = std::move(offsets);
+  g->hist = std::move(hist);
+  g->n_ids = kept;
+  g->mapped = true;
+  return W2V_OK;
 }
 
 int w2v_ingest_samples_size(w2v_ingest* g, int64_t* n_ids, int64_t* n_sentences, int64_t* train_words) {
-  if (!g) return fail_i(W2V_ERR_ARG, "null ingest");
-  if (!g->mapped) return fail_i(W2V_ERR_STATE, "w2v_ingest_map first");
+  if (!g) return w2v::set_error(W2V_ERR_ARG, "null ingest");
+  if (!g->mapped) return w2v::set_error(W2V_ERR_STATE, "w2v_ingest_map first");
   if (n_ids) *n_ids = g->n_ids;
   if (n_sentences) *n_sentences = g->n_sentences;
   if (train_words) *train_words = g->raw_tokens;
@@ -869,11 +835,11 @@ int w2v_ingest_samples_size(w2v_ingest* g, int64_t* n_ids, int64_t* n_sentences,
 }
 
 int w2v_ingest_download(w2v_ingest* g, int32_t* ids, int64_t* offsets) {
-  if (!g) return fail_i(W2V_ERR_ARG, "null ingest");
-  if (!g->mapped) return fail_i(W2V_ERR_STATE, "w2v_ingest_map first");
-  HIP_I(hipSetDevice(g->device));
-  if (ids && g->n_ids > 0) HIP_I(hipMemcpy(ids, g->ids, g->n_ids * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (offsets) HIP_I(hipMemcpy(offsets, g->offsets, (g->n_sentences + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+  if (!g) return w2v::set_error(W2V_ERR_ARG, "null ingest");
+  if (!g->mapped) return w2v::set_error(W2V_ERR_STATE, "w2v_ingest_map first");
+  W2V_HIP_TRY(hipSetDevice(g->device));
+  if (ids && g->n_ids > 0) W2V_HIP_TRY(hipMemcpy(ids, g->ids.get(), g->n_ids * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (offsets) W2V_HIP_TRY(hipMemcpy(offsets, g->offsets.get(), (g->n_sentences + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
   return W2V_OK;
 }
 
@@ -884,9 +850,9 @@ IngestView ingest_view(const w2v_ingest* g) {
   IngestView v{};
   if (!g || !g->mapped) return v;
   v.device = g->device;
-  v.ids = g->ids;
+  v.ids = g->ids.get();
   v.n_ids = g->n_ids;
-  v.offsets = g->offsets;
+  v.offsets = g->offsets.get();
   v.n_sentences = g->n_sentences;
   v.train_words = g->raw_tokens;
   v.hist = g->hist.data();

@@ -54,6 +54,7 @@
 #include <cmath>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <string>
 
 #include "w2v_dev.h"
@@ -396,62 +397,42 @@ struct w2v_nn {
   hipStream_t stream = nullptr;
   w2v_dev* h = nullptr;  // attached: the handle whose matrix is borrowed
   int32_t which = 0;
-  float* rows = nullptr;  // owned unless h
+  const float* rows = nullptr;   // the matrix the kernels read: the handle's, or rows_own
+  w2v::DevBuf<float> rows_own;  // empty when attached
   int64_t n_rows = 0;
   int32_t dim = 0;
   int32_t cols = 0;  // dim rounded up to 16
   int64_t pitch = 0;
-  float* inv_norm = nullptr;
-  // scratch, grown on demand (bytes)
-  void* q = nullptr;       size_t q_cap = 0;
-  void* ids = nullptr;     size_t ids_cap = 0;
-  void* wts = nullptr;     size_t wts_cap = 0;
-  void* p_score = nullptr; size_t p_score_cap = 0;
-  void* p_id = nullptr;    size_t p_id_cap = 0;
-  void* o_score = nullptr; size_t o_score_cap = 0;
-  void* o_id = nullptr;    size_t o_id_cap = 0;
+  w2v::DevBuf<float> inv_norm;
+  // scratch, grown on demand
+  w2v::DevBuf<float> q, wts, p_score, o_score;
+  w2v::DevBuf<int32_t> ids, p_id, o_id;
   int64_t strip_rows_set = 0;
   int64_t plan_strips = 0, plan_strip_rows = 0;
+
+  ~w2v_nn() {  // the buffers free themselves after this
+    (void)hipSetDevice(device);
+    if (stream) {
+      (void)hipStreamSynchronize(stream);
+      (void)hipStreamDestroy(stream);
+    }
+  }
 };
 
 namespace {
 
-#define HIP_N(expr)                                                                           \
-  do {                                                                                        \
-    hipError_t e_ = (expr);                                                                   \
-    if (e_ != hipSuccess)                                                                     \
-      return w2v::set_error(W2V_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));  \
-  } while (0)
-
-int nn_fail(const std::string& msg) { return w2v::set_error(W2V_ERR_ARG, msg); }
-
-int grow(void*& p, size_t& cap, size_t need) {
-  if (need <= cap) return W2V_OK;
-  if (p) (void)hipFree(p);
-  p = nullptr;
-  cap = 0;
-  HIP_N(hipMalloc(&p, need));
-  cap = need;
-  return W2V_OK;
+template <class T>
+int grow(w2v::DevBuf<T>& b, size_t need) {
+  return need <= b.size() ? W2V_OK : b.alloc(need);
 }
 
 int compute_norms(w2v_nn* x) {
   const unsigned grid = (unsigned)((x->n_rows + w2v::kNnWaves - 1) / w2v::kNnWaves);
   hipLaunchKernelGGL(w2v::nn_norm_kernel, dim3(grid), dim3(256), 0, x->stream, x->rows, x->n_rows, x->pitch, x->cols,
-                     x->inv_norm);
-  HIP_N(hipGetLastError());
-  HIP_N(hipStreamSynchronize(x->stream));
+                     x->inv_norm.get());
+  W2V_HIP_TRY(hipGetLastError());
+  W2V_HIP_TRY(hipStreamSynchronize(x->stream));
   return W2V_OK;
-}
-
-void release(w2v_nn* x) {
-  if (!x) return;
-  (void)hipSetDevice(x->device);
-  if (!x->h && x->rows) (void)hipFree(x->rows);
-  for (void* p : {(void*)x->inv_norm, x->q, x->ids, x->wts, x->p_score, x->p_id, x->o_score, x->o_id})
-    if (p) (void)hipFree(p);
-  if (x->stream) (void)hipStreamDestroy(x->stream);
-  delete x;
 }
 
 using ScoreFn = void (*)(w2v::NnArgs);
@@ -484,14 +465,14 @@ int query_block_for(int cols) {
 int run_chunk(w2v_nn* x, int64_t n, bool by_row, int32_t terms, const int32_t* excl_d, int32_t n_excl, int64_t limit,
               int32_t k, int64_t strip_rows, int64_t strips, int32_t* out_ids, float* out_scores) {
   const unsigned qgrid = (unsigned)((n + w2v::kNnWaves - 1) / w2v::kNnWaves);
-  hipLaunchKernelGGL(w2v::nn_query_kernel, dim3(qgrid), dim3(256), 0, x->stream, x->rows, x->pitch, x->inv_norm,
-                     by_row ? (const int32_t*)x->ids : (const int32_t*)nullptr, (const float*)x->wts, terms,
-                     (float*)x->q, n, x->cols);
-  HIP_N(hipGetLastError());
+  hipLaunchKernelGGL(w2v::nn_query_kernel, dim3(qgrid), dim3(256), 0, x->stream, x->rows, x->pitch,
+                     x->inv_norm.get(), by_row ? x->ids.get() : (const int32_t*)nullptr, x->wts.get(), terms,
+                     x->q.get(), n, x->cols);
+  W2V_HIP_TRY(hipGetLastError());
   w2v::NnArgs a{};
   a.rows = x->rows;
-  a.inv_norm = x->inv_norm;
-  a.q = (const float*)x->q;
+  a.inv_norm = x->inv_norm.get();
+  a.q = x->q.get();
   a.excl = excl_d;
   a.n_excl = n_excl;
   a.pitch = x->pitch;
@@ -503,18 +484,18 @@ int run_chunk(w2v_nn* x, int64_t n, bool by_row, int32_t terms, const int32_t* e
   const int qblock = query_block_for(x->cols);
   a.nqb = (int32_t)((n + qblock - 1) / qblock);
   a.k = k;
-  a.p_score = (float*)x->p_score;
-  a.p_id = (int32_t*)x->p_id;
+  a.p_score = x->p_score.get();
+  a.p_id = x->p_id.get();
   const size_t lds = (size_t)2 * qblock * k * sizeof(float);  // a (score, id) list of k per query
   int qb_ = 0;
   hipLaunchKernelGGL(score_kernel_for(x->cols, &qb_), dim3((unsigned)(strips * a.nqb)), dim3(256), lds, x->stream, a);
-  HIP_N(hipGetLastError());
-  hipLaunchKernelGGL(w2v::nn_merge_kernel, dim3(qgrid), dim3(256), 0, x->stream, (const float*)x->p_score,
-                     (const int32_t*)x->p_id, strips * k, k, n, (float*)x->o_score, (int32_t*)x->o_id);
-  HIP_N(hipGetLastError());
-  HIP_N(hipMemcpyAsync(out_ids, x->o_id, (size_t)n * k * sizeof(int32_t), hipMemcpyDeviceToHost, x->stream));
-  HIP_N(hipMemcpyAsync(out_scores, x->o_score, (size_t)n * k * sizeof(float), hipMemcpyDeviceToHost, x->stream));
-  HIP_N(hipStreamSynchronize(x->stream));
+  W2V_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(w2v::nn_merge_kernel, dim3(qgrid), dim3(256), 0, x->stream, x->p_score.get(), x->p_id.get(),
+                     strips * k, k, n, x->o_score.get(), x->o_id.get());
+  W2V_HIP_TRY(hipGetLastError());
+  W2V_HIP_TRY(hipMemcpyAsync(out_ids, x->o_id.get(), (size_t)n * k * sizeof(int32_t), hipMemcpyDeviceToHost, x->stream));
+  W2V_HIP_TRY(hipMemcpyAsync(out_scores, x->o_score.get(), (size_t)n * k * sizeof(float), hipMemcpyDeviceToHost, x->stream));
+  W2V_HIP_TRY(hipStreamSynchronize(x->stream));
   return W2V_OK;
 }
 
@@ -536,46 +517,46 @@ int run_query(w2v_nn* x, const float* q, const int32_t* ids, const float* weight
   const int64_t strips = (limit + strip_rows - 1) / strip_rows;
   // a query block is the least a launch takes: its partial lists must fit their budget
   if (strips * k * qblock * (int64_t)sizeof(float) > w2v::kNnPartialBytes)
-    return nn_fail("w2v_nn query: " + std::to_string(strips) + " strips of " + std::to_string(strip_rows) +
+    return w2v::set_error(W2V_ERR_ARG, "w2v_nn query: " + std::to_string(strips) + " strips of " + std::to_string(strip_rows) +
                    " rows at k " + std::to_string(k) + " need more than " +
                    std::to_string(w2v::kNnPartialBytes >> 20) + " MiB of partial lists per query block; set a larger "
                    "strip (w2v_nn_set_strip_rows; 0 = automatic)");
   if (strips * nqb > (int64_t)0x7fffffff)
-    return nn_fail("w2v_nn query: too many strips x query blocks for one grid; set a larger strip (w2v_nn_set_strip_rows)");
+    return w2v::set_error(W2V_ERR_ARG, "w2v_nn query: too many strips x query blocks for one grid; set a larger strip (w2v_nn_set_strip_rows)");
   x->plan_strips = strips;
   x->plan_strip_rows = strip_rows;
   if (nq == 0) return W2V_OK;
-  HIP_N(hipSetDevice(x->device));
+  W2V_HIP_TRY(hipSetDevice(x->device));
   // queries per chunk: what keeps the partial buffers within their budget
   int64_t chunk = w2v::kNnPartialBytes / (strips * k * (int64_t)sizeof(float));
   chunk = std::max<int64_t>(qblock, std::min(chunk, w2v::kNnChunkQueries) / qblock * qblock);
   chunk = std::min(chunk, (nq + qblock - 1) / qblock * qblock);
   int rc;
-  const size_t q_bytes = (size_t)chunk * x->cols * sizeof(float);
-  if ((rc = grow(x->q, x->q_cap, q_bytes))) return rc;
-  if ((rc = grow(x->p_score, x->p_score_cap, (size_t)chunk * strips * k * sizeof(float)))) return rc;
-  if ((rc = grow(x->p_id, x->p_id_cap, (size_t)chunk * strips * k * sizeof(int32_t)))) return rc;
-  if ((rc = grow(x->o_score, x->o_score_cap, (size_t)chunk * k * sizeof(float)))) return rc;
-  if ((rc = grow(x->o_id, x->o_id_cap, (size_t)chunk * k * sizeof(int32_t)))) return rc;
+  const size_t q_n = (size_t)chunk * x->cols, q_bytes = q_n * sizeof(float);
+  if ((rc = grow(x->q, q_n))) return rc;
+  if ((rc = grow(x->p_score, (size_t)chunk * strips * k))) return rc;
+  if ((rc = grow(x->p_id, (size_t)chunk * strips * k))) return rc;
+  if ((rc = grow(x->o_score, (size_t)chunk * k))) return rc;
+  if ((rc = grow(x->o_id, (size_t)chunk * k))) return rc;
   const int32_t n_ids = q ? n_excl : terms;  // ids per query in x->ids: the exclusions, or the terms
-  if (n_ids > 0 && (rc = grow(x->ids, x->ids_cap, (size_t)chunk * n_ids * sizeof(int32_t)))) return rc;
-  if (!q && (rc = grow(x->wts, x->wts_cap, (size_t)chunk * terms * sizeof(float)))) return rc;
+  if (n_ids > 0 && (rc = grow(x->ids, (size_t)chunk * n_ids))) return rc;
+  if (!q && (rc = grow(x->wts, (size_t)chunk * terms))) return rc;
   for (int64_t c0 = 0; c0 < nq; c0 += chunk) {
     const int64_t n = std::min(chunk, nq - c0);
-    HIP_N(hipMemsetAsync(x->q, 0, q_bytes, x->stream));  // padding columns and tail queries are zero
+    W2V_HIP_TRY(hipMemsetAsync(x->q.get(), 0, q_bytes, x->stream));  // padding columns and tail queries are zero
     if (q) {
-      HIP_N(hipMemcpy2DAsync(x->q, (size_t)x->cols * sizeof(float), q + c0 * x->dim, (size_t)x->dim * sizeof(float),
+      W2V_HIP_TRY(hipMemcpy2DAsync(x->q.get(), (size_t)x->cols * sizeof(float), q + c0 * x->dim, (size_t)x->dim * sizeof(float),
                              (size_t)x->dim * sizeof(float), (size_t)n, hipMemcpyHostToDevice, x->stream));
       if (n_excl > 0)
-        HIP_N(hipMemcpyAsync(x->ids, exclude + c0 * n_excl, (size_t)n * n_excl * sizeof(int32_t),
+        W2V_HIP_TRY(hipMemcpyAsync(x->ids.get(), exclude + c0 * n_excl, (size_t)n * n_excl * sizeof(int32_t),
                              hipMemcpyHostToDevice, x->stream));
     } else {
-      HIP_N(hipMemcpyAsync(x->ids, ids + c0 * terms, (size_t)n * terms * sizeof(int32_t), hipMemcpyHostToDevice,
+      W2V_HIP_TRY(hipMemcpyAsync(x->ids.get(), ids + c0 * terms, (size_t)n * terms * sizeof(int32_t), hipMemcpyHostToDevice,
                            x->stream));
-      HIP_N(hipMemcpyAsync(x->wts, weights + c0 * terms, (size_t)n * terms * sizeof(float), hipMemcpyHostToDevice,
+      W2V_HIP_TRY(hipMemcpyAsync(x->wts.get(), weights + c0 * terms, (size_t)n * terms * sizeof(float), hipMemcpyHostToDevice,
                            x->stream));
     }
-    rc = run_chunk(x, n, q == nullptr, terms, n_ids > 0 ? (const int32_t*)x->ids : nullptr, n_ids, limit, k,
+    rc = run_chunk(x, n, q == nullptr, terms, n_ids > 0 ? x->ids.get() : nullptr, n_ids, limit, k,
                    strip_rows, strips, out_ids + c0 * k, out_scores + c0 * k);
     if (rc) return rc;
   }
@@ -585,11 +566,11 @@ int run_query(w2v_nn* x, const float* q, const int32_t* ids, const float* weight
 int check_common(const char* fn, w2v_nn* x, int64_t nq, int64_t restrict_rows, int32_t k, const int32_t* out_ids,
                  const float* out_scores) {
   const std::string f(fn);
-  if (!x) return nn_fail(f + ": null index");
-  if (nq < 0) return nn_fail(f + ": nq must be >= 0");
-  if (k < 1 || k > w2v::kNnMaxK) return nn_fail(f + ": k must be in [1, " + std::to_string(w2v::kNnMaxK) + "], got " + std::to_string(k));
-  if (restrict_rows < 0) return nn_fail(f + ": restrict_rows must be >= 0 (0 = all rows)");
-  if (nq > 0 && (!out_ids || !out_scores)) return nn_fail(f + ": null output");
+  if (!x) return w2v::set_error(W2V_ERR_ARG, f + ": null index");
+  if (nq < 0) return w2v::set_error(W2V_ERR_ARG, f + ": nq must be >= 0");
+  if (k < 1 || k > w2v::kNnMaxK) return w2v::set_error(W2V_ERR_ARG, f + ": k must be in [1, " + std::to_string(w2v::kNnMaxK) + "], got " + std::to_string(k));
+  if (restrict_rows < 0) return w2v::set_error(W2V_ERR_ARG, f + ": restrict_rows must be >= 0 (0 = all rows)");
+  if (nq > 0 && (!out_ids || !out_scores)) return w2v::set_error(W2V_ERR_ARG, f + ": null output");
   return W2V_OK;
 }
 
@@ -605,79 +586,62 @@ int w2v_nn_limits(int32_t* max_dim, int32_t* max_k, int32_t* max_terms) {
 }
 
 int w2v_nn_create(int32_t device, const float* rows, int64_t n_rows, int32_t dim, w2v_nn** out) {
-  if (!out) return nn_fail("w2v_nn_create: null output");
+  if (!out) return w2v::set_error(W2V_ERR_ARG, "w2v_nn_create: null output");
   *out = nullptr;
-  if (!rows) return nn_fail("w2v_nn_create: null matrix");
+  if (!rows) return w2v::set_error(W2V_ERR_ARG, "w2v_nn_create: null matrix");
   if (dim < 1 || dim > w2v::kNnMaxDim)
-    return nn_fail("w2v_nn_create: dim must be in [1, " + std::to_string(w2v::kNnMaxDim) + "], got " + std::to_string(dim));
+    return w2v::set_error(W2V_ERR_ARG, "w2v_nn_create: dim must be in [1, " + std::to_string(w2v::kNnMaxDim) + "], got " + std::to_string(dim));
   if (n_rows < 1 || n_rows > (int64_t)0x7fffffff)
-    return nn_fail("w2v_nn_create: n_rows must be in [1, 2^31), got " + std::to_string(n_rows));
+    return w2v::set_error(W2V_ERR_ARG, "w2v_nn_create: n_rows must be in [1, 2^31), got " + std::to_string(n_rows));
   w2v::Range range_("w2v_nn_create");
-  if (device >= 0) HIP_N(hipSetDevice(device));
+  if (device >= 0) W2V_HIP_TRY(hipSetDevice(device));
   int dev = 0;
-  HIP_N(hipGetDevice(&dev));
-  w2v_nn* x = new w2v_nn();
+  W2V_HIP_TRY(hipGetDevice(&dev));
+  std::unique_ptr<w2v_nn> x(new w2v_nn());
   x->device = dev;
   x->n_rows = n_rows;
   x->dim = dim;
   x->cols = (dim + 15) & ~15;
   x->pitch = x->cols;
-  auto bail = [&](hipError_t e, const char* what) {
-    release(x);
-    return w2v::set_error(W2V_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-  };
-  hipError_t e;
-  if ((e = hipStreamCreateWithFlags(&x->stream, hipStreamNonBlocking)) != hipSuccess) return bail(e, "hipStreamCreate");
-  const size_t bytes = (size_t)n_rows * x->pitch * sizeof(float);
-  if ((e = hipMalloc((void**)&x->rows, bytes)) != hipSuccess) return bail(e, "hipMalloc (rows)");
-  if ((e = hipMalloc((void**)&x->inv_norm, (size_t)n_rows * sizeof(float))) != hipSuccess) return bail(e, "hipMalloc (inv_norm)");
-  if ((e = hipMemsetAsync(x->rows, 0, bytes, x->stream)) != hipSuccess) return bail(e, "hipMemsetAsync");
-  if ((e = hipMemcpy2DAsync(x->rows, (size_t)x->pitch * sizeof(float), rows, (size_t)dim * sizeof(float),
-                            (size_t)dim * sizeof(float), (size_t)n_rows, hipMemcpyHostToDevice, x->stream)) != hipSuccess)
-    return bail(e, "hipMemcpy2DAsync");
-  const int rc = compute_norms(x);
-  if (rc) {
-    release(x);
-    return rc;
-  }
-  *out = x;
+  W2V_HIP_TRY(hipStreamCreateWithFlags(&x->stream, hipStreamNonBlocking));
+  const size_t n = (size_t)n_rows * x->pitch;
+  int rc;
+  if ((rc = x->rows_own.alloc(n)) || (rc = x->inv_norm.alloc((size_t)n_rows))) return rc;
+  x->rows = x->rows_own.get();
+  W2V_HIP_TRY(hipMemsetAsync(x->rows_own.get(), 0, n * sizeof(float), x->stream));
+  W2V_HIP_TRY(hipMemcpy2DAsync(x->rows_own.get(), (size_t)x->pitch * sizeof(float), rows, (size_t)dim * sizeof(float),
+                               (size_t)dim * sizeof(float), (size_t)n_rows, hipMemcpyHostToDevice, x->stream));
+  if ((rc = compute_norms(x.get()))) return rc;
+  *out = x.release();
   return W2V_OK;
 }
 
 int w2v_nn_attach(w2v_dev* h, int32_t which, w2v_nn** out) {
   w2v::Range range_("w2v_nn_attach");
-  if (!out) return nn_fail("w2v_nn_attach: null output");
+  if (!out) return w2v::set_error(W2V_ERR_ARG, "w2v_nn_attach: null output");
   *out = nullptr;
-  if (!h) return nn_fail("w2v_nn_attach: null handle");
-  if (which != 0 && which != 1) return nn_fail("w2v_nn_attach: which must be 0 (W) or 1 (C)");
+  if (!h) return w2v::set_error(W2V_ERR_ARG, "w2v_nn_attach: null handle");
+  if (which != 0 && which != 1) return w2v::set_error(W2V_ERR_ARG, "w2v_nn_attach: which must be 0 (W) or 1 (C)");
   const w2v::DevInfo info = w2v::dev_info(h);
   if (info.V < 1) return w2v::set_error(W2V_ERR_STATE, "w2v_nn_attach: the handle has no vocabulary yet");
-  HIP_N(hipSetDevice(info.device));
-  w2v_nn* x = new w2v_nn();
+  W2V_HIP_TRY(hipSetDevice(info.device));
+  std::unique_ptr<w2v_nn> x(new w2v_nn());
   x->device = info.device;
   x->h = h;
   x->which = which;
   x->n_rows = info.V;
   x->dim = info.dim;
   x->cols = (info.dim + 15) & ~15;
-  hipError_t e;
-  if ((e = hipStreamCreateWithFlags(&x->stream, hipStreamNonBlocking)) != hipSuccess ||
-      (e = hipMalloc((void**)&x->inv_norm, (size_t)x->n_rows * sizeof(float))) != hipSuccess) {
-    release(x);
-    return w2v::set_error(W2V_ERR_HIP, std::string("w2v_nn_attach: ") + hipGetErrorString(e));
-  }
-  const int rc = w2v_nn_refresh(x);
-  if (rc) {
-    release(x);
-    return rc;
-  }
-  *out = x;
+  W2V_HIP_TRY(hipStreamCreateWithFlags(&x->stream, hipStreamNonBlocking));
+  int rc;
+  if ((rc = x->inv_norm.alloc((size_t)x->n_rows)) || (rc = w2v_nn_refresh(x.get()))) return rc;
+  *out = x.release();
   return W2V_OK;
 }
 
 int w2v_nn_refresh(w2v_nn* x) {
-  if (!x) return nn_fail("w2v_nn_refresh: null index");
-  HIP_N(hipSetDevice(x->device));
+  if (!x) return w2v::set_error(W2V_ERR_ARG, "w2v_nn_refresh: null index");
+  W2V_HIP_TRY(hipSetDevice(x->device));
   if (x->h) {
     int rc = w2v_dev_synchronize(x->h);  // the training enqueued on the handle's stream
     if (rc) return rc;
@@ -693,17 +657,17 @@ int w2v_nn_refresh(w2v_nn* x) {
   return compute_norms(x);
 }
 
-void w2v_nn_destroy(w2v_nn* x) { release(x); }
+void w2v_nn_destroy(w2v_nn* x) { delete x; }
 
 int w2v_nn_set_strip_rows(w2v_nn* x, int64_t rows) {
-  if (!x) return nn_fail("w2v_nn_set_strip_rows: null index");
-  if (rows < 0 || rows % 16 != 0) return nn_fail("w2v_nn_set_strip_rows: rows must be 0 (auto) or a positive multiple of 16");
+  if (!x) return w2v::set_error(W2V_ERR_ARG, "w2v_nn_set_strip_rows: null index");
+  if (rows < 0 || rows % 16 != 0) return w2v::set_error(W2V_ERR_ARG, "w2v_nn_set_strip_rows: rows must be 0 (auto) or a positive multiple of 16");
   x->strip_rows_set = rows;
   return W2V_OK;
 }
 
 int w2v_nn_plan(w2v_nn* x, int64_t* strips, int32_t* query_block, int64_t* strip_rows) {
-  if (!x) return nn_fail("w2v_nn_plan: null index");
+  if (!x) return w2v::set_error(W2V_ERR_ARG, "w2v_nn_plan: null index");
   if (strips) *strips = x->plan_strips;
   if (query_block) *query_block = query_block_for(x->cols);
   if (strip_rows) *strip_rows = x->plan_strip_rows;
@@ -715,8 +679,8 @@ int w2v_nn_query_vectors(w2v_nn* x, const float* q, int64_t nq, const int32_t* e
   w2v::Range range_("w2v_nn_query_vectors");
   const int rc = check_common("w2v_nn_query_vectors", x, nq, restrict_rows, k, out_ids, out_scores);
   if (rc) return rc;
-  if (nq > 0 && !q) return nn_fail("w2v_nn_query_vectors: null queries");
-  if (n_excl < 0) return nn_fail("w2v_nn_query_vectors: n_excl must be >= 0");
+  if (nq > 0 && !q) return w2v::set_error(W2V_ERR_ARG, "w2v_nn_query_vectors: null queries");
+  if (n_excl < 0) return w2v::set_error(W2V_ERR_ARG, "w2v_nn_query_vectors: n_excl must be >= 0");
   if (!exclude) n_excl = 0;
   return run_query(x, q, nullptr, nullptr, 0, nq, exclude, n_excl, restrict_rows, k, out_ids, out_scores);
 }
@@ -727,11 +691,11 @@ int w2v_nn_query_rows(w2v_nn* x, const int32_t* ids, const float* weights, int32
   const int rc = check_common("w2v_nn_query_rows", x, nq, restrict_rows, k, out_ids, out_scores);
   if (rc) return rc;
   if (terms < 1 || terms > w2v::kNnMaxTerms)
-    return nn_fail("w2v_nn_query_rows: terms must be in [1, " + std::to_string(w2v::kNnMaxTerms) + "], got " + std::to_string(terms));
-  if (nq > 0 && (!ids || !weights)) return nn_fail("w2v_nn_query_rows: null ids or weights");
+    return w2v::set_error(W2V_ERR_ARG, "w2v_nn_query_rows: terms must be in [1, " + std::to_string(w2v::kNnMaxTerms) + "], got " + std::to_string(terms));
+  if (nq > 0 && (!ids || !weights)) return w2v::set_error(W2V_ERR_ARG, "w2v_nn_query_rows: null ids or weights");
   for (int64_t i = 0; i < nq * terms; ++i)
     if (ids[i] >= x->n_rows)
-      return nn_fail("w2v_nn_query_rows: row id " + std::to_string(ids[i]) + " outside [0, " + std::to_string(x->n_rows) + ")");
+      return w2v::set_error(W2V_ERR_ARG, "w2v_nn_query_rows: row id " + std::to_string(ids[i]) + " outside [0, " + std::to_string(x->n_rows) + ")");
   return run_query(x, nullptr, ids, weights, terms, nq, nullptr, 0, restrict_rows, k, out_ids, out_scores);
 }
 
