@@ -256,6 +256,14 @@ class Word2Vec {
   void most_similar_ids(const int32_t* ids, const float* weights, int terms, int64_t restrict_vocab, int k,
                         int32_t* out_ids, float* out_scores);
   void drop_index();
+  // Word classes (word2vec's -classes): k-means over the rows of `data` on the
+  // device (include/w2v_dev.h, w2v_nn_classes: start r mod n_classes, at most
+  // `iterations` iterations), one class id per row; -1 for a row with a
+  // non-finite element. Uses the cached index when `data` is W, a temporary
+  // one otherwise. save_classes writes one "word class" line per vocabulary
+  // word, in vocabulary order (word2vec.c's format). Errors as most_similar's.
+  std::vector<int32_t> word_classes(const RMatrixXf& data, int n_classes, int iterations = 10);
+  void save_classes(const std::string& filename, const RMatrixXf& data, int n_classes, int iterations = 10);
   // Last device error (empty if none).
   std::string last_error;
 

@@ -524,6 +524,50 @@ int w2v_nn_query_vectors(w2v_nn* x, const float* q, int64_t nq, const int32_t* e
 int w2v_nn_query_rows(w2v_nn* x, const int32_t* ids, const float* weights, int32_t terms, int64_t nq,
                       int64_t restrict_rows, int32_t k, int32_t* out_ids, float* out_scores);
 
+/* Word classes (word2vec's -classes): spherical k-means over the rows of an
+ * index, owned or attached, with n_classes classes.
+ *
+ * Start: class[r] = r mod n_classes. Each iteration first updates
+ * (centroid[c] = the sum of the raw rows of the members of c, scaled to unit
+ * length by x / max(|x|, 1e-12)), then assigns (class[r] = the class whose
+ * unit centroid has the highest cosine with row r; the score is (row .
+ * centroid) * inv_norm[r]; equal scores go to the lowest class id). A centroid
+ * that is all zero (an empty class, or members that cancel) or holds a
+ * non-finite value takes no rows. A row with a non-finite element is a member
+ * of nothing, from the start and in every update, and is reported as class -1
+ * with score -inf, as is every row when no valid centroid exists; a zero row
+ * scores 0 everywhere and goes to the lowest valid class. The run stops after
+ * `iterations` iterations, or earlier after one that moved no row.
+ *
+ * Deterministic as the queries are: a (row, centroid) score has one
+ * accumulation order, the centroid sums use no float atomics and their order
+ * is a function of the class array, n_classes and constants only; the same
+ * call returns the same bits, and duplicate rows get the same class and score
+ * bits. Every step scales the centroids it is given to unit length
+ * (w2v_nn_classes too, between its own update and assign), so w2v_nn_classes
+ * is bit for bit w2v_nn_centroids then w2v_nn_assign, repeated from r mod
+ * n_classes. 1 <= n_classes <= min(n_rows, 65536), 1 <= iterations <= 1000.
+ *
+ * w2v_nn_assign: one assignment step against the caller's centroids (host,
+ * n_classes x dim, any length). out_score may be NULL.
+ * w2v_nn_centroids: one update step: the unit centroids (a zero row for a
+ * class without members) and member counts of the caller's classes (host,
+ * n_rows ids in [-1, n_classes); -1 = member of nothing; a non-finite row is
+ * left out whatever its id). out_count may be NULL.
+ * w2v_nn_classes: the whole run. Returns the final classes, their scores, the
+ * centroids they were scored against, the member counts of the final classes,
+ * the rows moved per iteration (`iterations` entries, 0 past the last one run)
+ * and the iterations run; every output but out_class may be NULL.
+ * w2v_nn_class_times: the device time (event timestamps around each step's
+ * kernels, in ms) of the update and the assign steps of the calling thread's
+ * last w2v_nn_classes, summed over its iterations (tools/classes_bench.py). */
+int w2v_nn_class_limits(int32_t* max_classes, int32_t* max_iterations);
+int w2v_nn_class_times(double* update_ms, double* assign_ms);
+int w2v_nn_assign(w2v_nn* x, const float* centroids, int32_t n_classes, int32_t* out_class, float* out_score);
+int w2v_nn_centroids(w2v_nn* x, const int32_t* cls, int32_t n_classes, float* out_centroids, int64_t* out_count);
+int w2v_nn_classes(w2v_nn* x, int32_t n_classes, int32_t iterations, int32_t* out_class, float* out_score,
+                   float* out_centroids, int64_t* out_count, int64_t* out_moved, int32_t* iterations_run);
+
 #ifdef __cplusplus
 }
 #endif

@@ -100,6 +100,12 @@ int w2v_model_most_similar_words(w2v_model* m, const char* positive, const char*
 int w2v_model_analogy(w2v_model* m, const char* a, const char* b, const char* c, int32_t topn,
                       int64_t restrict_rows, int32_t* out_ids, float* out_scores, int32_t* n_out);
 
+/* Word2Vec::word_classes (word2vec's -classes): k-means over the rows of W
+ * (which 0), C (1) or synapses1 (2) on the device, from class r mod n_classes,
+ * at most `iterations` iterations (include/w2v_dev.h w2v_nn_classes). out takes
+ * one class id per row (-1 for a row with a non-finite element). */
+int w2v_model_word_classes(w2v_model* m, int32_t which, int32_t n_classes, int32_t iterations, int32_t* out);
+
 int w2v_model_save(w2v_model* m, const char* path, int32_t which, int32_t binary);
 int w2v_model_load(w2v_model* m, const char* path, int32_t binary);
 int w2v_model_save_vocab(w2v_model* m, const char* path);

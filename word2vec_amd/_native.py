@@ -169,6 +169,12 @@ SIGNATURES = {
     "w2v_nn_plan": (C.c_int, [_P, C.POINTER(_I64), C.POINTER(_I32), C.POINTER(_I64)]),
     "w2v_nn_query_vectors": (C.c_int, [_P, _P, _I64, _P, _I32, _I64, _I32, _P, _P]),
     "w2v_nn_query_rows": (C.c_int, [_P, _P, _P, _I32, _I64, _I64, _I32, _P, _P]),
+    # word classes: k-means over an index's rows
+    "w2v_nn_class_limits": (C.c_int, [C.POINTER(_I32)] * 2),
+    "w2v_nn_class_times": (C.c_int, [C.POINTER(C.c_double)] * 2),
+    "w2v_nn_assign": (C.c_int, [_P, _P, _I32, _P, _P]),
+    "w2v_nn_centroids": (C.c_int, [_P, _P, _I32, _P, _P]),
+    "w2v_nn_classes": (C.c_int, [_P, _I32, _I32, _P, _P, _P, _P, _P, C.POINTER(_I32)]),
     # include/w2v_ingest.h
     "w2v_ingest_create": (C.c_int, [_I32, _I32, _I64, C.POINTER(_P)]),
     "w2v_ingest_destroy": (None, [_P]),

@@ -888,6 +888,38 @@ std::vector<std::pair<std::string, float>> Word2Vec::analogy(const std::string& 
 }
 
 // ---------------------------------------------------------------------------
+// Word classes (additive): word2vec's -classes, k-means on the device.
+// ---------------------------------------------------------------------------
+std::vector<int32_t> Word2Vec::word_classes(const RMatrixXf& data, int n_classes, int iterations) {
+  std::vector<int32_t> out((size_t)data.rows(), -1);
+  w2v_nn* x = nullptr;
+  const bool cached = &data == &W;
+  if (cached) {
+    if (!nn_)
+      check(w2v_nn_create(gpu_device, W.data(), (int64_t)W.rows(), (int32_t)W.cols(), &nn_), "word_classes (w2v_nn_create)");
+    x = nn_;
+  } else {
+    check(w2v_nn_create(gpu_device, data.data(), (int64_t)data.rows(), (int32_t)data.cols(), &x),
+          "word_classes (w2v_nn_create)");
+  }
+  const int rc = w2v_nn_classes(x, n_classes, iterations, out.data(), nullptr, nullptr, nullptr, nullptr, nullptr);
+  if (!cached) w2v_nn_destroy(x);  // keeps the calling thread's last error
+  check(rc, "word_classes (w2v_nn_classes)");
+  return out;
+}
+
+void Word2Vec::save_classes(const std::string& filename, const RMatrixXf& data, int n_classes, int iterations) {
+  if ((size_t)data.rows() != vocab.size()) {
+    last_error = "save_classes: the matrix has " + std::to_string(data.rows()) + " rows, the vocabulary " +
+                 std::to_string(vocab.size()) + " words";
+    throw std::runtime_error("word2vec_amd: " + last_error);
+  }
+  const std::vector<int32_t> cls = word_classes(data, n_classes, iterations);
+  std::ofstream out(filename, std::ofstream::out);
+  for (size_t i = 0; i < vocab.size(); ++i) out << vocab[i]->text << " " << cls[i] << "\n";
+}
+
+// ---------------------------------------------------------------------------
 // Vector files (Word2Vec.cpp:398-495), same bytes.
 // ---------------------------------------------------------------------------
 void Word2Vec::save_word2vec(std::string filename, const RMatrixXf& data, bool binary) {

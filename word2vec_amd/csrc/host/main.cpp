@@ -7,7 +7,8 @@
 // the pre-override 0.025 (:116), 1000-token sentences (:66), and which matrix
 // is written (:196-201). Additive: -train is honoured (the reference always
 // reads ./text8), -binary, -gpu, -replay, -shared-negatives, and the
-// multi-GPU flags -gpus, -sync-words, -overlap, -replica-mode (Word2Vec::gpu_devices), -gpu-ingest.
+// multi-GPU flags -gpus, -sync-words, -overlap, -replica-mode (Word2Vec::gpu_devices), -gpu-ingest,
+// and -classes (in the reference's help text, never parsed by its main).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -46,7 +47,9 @@ void usage() {
                "  -overlap <0|1>        overlap the averaging with the next round's training (default 1)\n"
                "  -replica-mode <auto|sum|average|row_average|adaptive> how the replicas' updates combine\n"
                "                        (default auto: average for <= 4 replicas of >= 256 M words each, else sum for 2, adaptive for more)\n"
-               "  -gpu-ingest <0|1>     count and map the corpus on the GPU (default 0: host threads)\n\n"
+               "  -gpu-ingest <0|1>     count and map the corpus on the GPU (default 0: host threads)\n"
+               "  -classes <int>        output word classes rather than word vectors: k-means over the vectors on the\n"
+               "                        GPU, one \"word class\" line per word (default 0: vectors are written)\n\n"
                "example: ./word2vec -train text8 -output vec.txt -size 300 -window 5 -subsample 1e-4 "
                "-negative 5 -model sg -train_method ns -iter 3\n";
 }
@@ -76,7 +79,7 @@ int main(int argc, char** argv) {
   float init_alpha = 0.025f, subsample_threshold = 0.0001f;
   const float min_alpha = init_alpha * 0.0001;
   const bool cbow_mean = true;
-  int binary = 0, gpu = 0, replay = 0, shared = 0, gpus = 1, overlap = 1, gpu_ingest = 0;
+  int binary = 0, gpu = 0, replay = 0, shared = 0, gpus = 1, overlap = 1, gpu_ingest = 0, classes = 0;
   long long sync_words = 0;
   std::string replica_mode = "auto";
   int i;
@@ -103,6 +106,11 @@ int main(int argc, char** argv) {
   if ((i = find_flag("-overlap", argc, argv)) > 0) overlap = std::atoi(argv[i + 1]);
   if ((i = find_flag("-replica-mode", argc, argv)) > 0) replica_mode = argv[i + 1];
   if ((i = find_flag("-gpu-ingest", argc, argv)) > 0) gpu_ingest = std::atoi(argv[i + 1]);
+  if ((i = find_flag("-classes", argc, argv)) > 0) classes = std::atoi(argv[i + 1]);
+  if (classes < 0) {
+    std::cout << "Please set -classes >= 0!" << std::endl;
+    return 1;
+  }
   if (gpus < 1 || sync_words < 0) {
     std::cout << "Please set -gpus >= 1 and -sync-words >= 0!" << std::endl;
     return 1;
@@ -193,8 +201,17 @@ int main(int argc, char** argv) {
     return 2;
   }
   if (!output_file.empty()) {
-    if (train_method == "hs" && model == "cbow") w2v.save_word2vec(output_file, w2v.C, binary != 0);
-    else w2v.save_word2vec(output_file, w2v.W, binary != 0);
+    const RMatrixXf& out = (train_method == "hs" && model == "cbow") ? w2v.C : w2v.W;
+    if (classes > 0) {
+      try {
+        w2v.save_classes(output_file, out, classes);
+      } catch (const std::exception& e) {
+        std::cerr << e.what() << std::endl;
+        return 2;
+      }
+    } else {
+      w2v.save_word2vec(output_file, out, binary != 0);
+    }
   }
   return 0;
 }

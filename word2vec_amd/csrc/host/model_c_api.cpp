@@ -269,6 +269,16 @@ int w2v_model_analogy(w2v_model* m, const char* a, const char* b, const char* c,
   });
 }
 
+int w2v_model_word_classes(w2v_model* m, int32_t which, int32_t n_classes, int32_t iterations, int32_t* out) {
+  return guard(m, [&] {
+    RMatrixXf* M = pick(m, which);
+    if (!M) throw std::invalid_argument("word_classes: bad matrix selector");
+    if (!out) throw std::invalid_argument("word_classes: null output");
+    const std::vector<int32_t> cls = m->w.word_classes(*M, n_classes, iterations);
+    if (!cls.empty()) std::memcpy(out, cls.data(), cls.size() * sizeof(int32_t));
+  });
+}
+
 int w2v_model_train_sentence(w2v_model* m, const int32_t* ids, int64_t n, float alpha, int32_t cbow) {
   return guard(m, [&] {
     std::vector<Word*> s;

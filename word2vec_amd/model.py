@@ -62,6 +62,7 @@ def _load():
             "w2v_model_most_similar": (C.c_int, [P, P, P, I32, I64, I32, P, P]),
             "w2v_model_most_similar_words": (C.c_int, [P, S, S, I32, I64, P, P, C.POINTER(I32)]),
             "w2v_model_analogy": (C.c_int, [P, S, S, S, I32, I64, P, P, C.POINTER(I32)]),
+            "w2v_model_word_classes": (C.c_int, [P, I32, I32, I32, P]),
             "w2v_model_save": (C.c_int, [P, S, I32, I32]),
             "w2v_model_load": (C.c_int, [P, S, I32]),
             "w2v_model_save_vocab": (C.c_int, [P, S]),
@@ -285,6 +286,15 @@ class Word2Vec:
         """Word2Vec::analogy: a is to b as c is to ...; [(word, cosine)]."""
         return self._answers(lambda o, s, n: self.L.w2v_model_analogy(
             self.h, a.encode(), b.encode(), c.encode(), int(topn), int(restrict_vocab), o, s, n), topn)
+
+    def word_classes(self, n_classes, iterations=10, which=0):
+        """Word2Vec::word_classes (word2vec's -classes): one class id (int32) per row of W (which 0), C (1) or
+        synapses1 (2), from k-means on the GPU (include/w2v_model.h)."""
+        rows = self.L.w2v_model_rows(self.h, int(which))
+        out = np.empty(max(int(rows), 0), np.int32)
+        self._chk(self.L.w2v_model_word_classes(self.h, int(which), int(n_classes), int(iterations), _p(out)),
+                  "word_classes")
+        return out
 
     # introspection ---------------------------------------------------------
     @property

@@ -26,6 +26,22 @@ def limits() -> dict:
     return {"max_dim": d.value, "max_k": k.value, "max_terms": t.value}
 
 
+def class_limits() -> dict:
+    """w2v_nn_class_limits: the most classes and iterations a k-means run takes."""
+    lib = N.load_dev_lib()
+    k, it = C.c_int32(), C.c_int32()
+    N.check(lib, lib.w2v_nn_class_limits(C.byref(k), C.byref(it)), "w2v_nn_class_limits")
+    return {"max_classes": k.value, "max_iterations": it.value}
+
+
+def class_times() -> dict:
+    """w2v_nn_class_times: device ms of the update and assign steps of this thread's last classes() run."""
+    lib = N.load_dev_lib()
+    u, a = C.c_double(), C.c_double()
+    N.check(lib, lib.w2v_nn_class_times(C.byref(u), C.byref(a)), "w2v_nn_class_times")
+    return {"update_ms": u.value, "assign_ms": a.value}
+
+
 def _ptr(a: np.ndarray | None):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
@@ -135,3 +151,44 @@ class NearestIndex:
         self._chk(self.lib.w2v_nn_query_rows(self.x, _ptr(ia), _ptr(wa), terms, nq, int(restrict), int(k),
                                              _ptr(out), _ptr(sc)), "w2v_nn_query_rows")
         return out, sc
+
+    # -- word classes (spherical k-means over the rows; include/w2v_dev.h) ----
+    def assign(self, centroids):
+        """One assignment step: (classes int32 [n_rows], scores float32 [n_rows]) of the rows against the
+        centroids (n_classes x dim, any length; a zero or non-finite centroid takes no rows). Highest cosine,
+        equal scores to the lowest class; -1 / -inf for a non-finite row or when no centroid is valid."""
+        ca = np.ascontiguousarray(centroids, dtype=np.float32)
+        if ca.ndim != 2 or ca.shape[1] != self.dim:
+            raise ValueError(f"assign: expected (n_classes, {self.dim}) centroids, got {ca.shape}")
+        cls = np.empty(self.n_rows, np.int32)
+        sc = np.empty(self.n_rows, np.float32)
+        self._chk(self.lib.w2v_nn_assign(self.x, _ptr(ca), ca.shape[0], _ptr(cls), _ptr(sc)), "w2v_nn_assign")
+        return cls, sc
+
+    def centroids(self, classes, n_classes: int):
+        """One update step: (unit centroids float32 [n_classes, dim], counts int64 [n_classes]) of the classes
+        (n_rows ids in [-1, n_classes); -1 and non-finite rows are members of nothing; a class without members
+        gets a zero row)."""
+        ca = np.ascontiguousarray(classes, dtype=np.int32)
+        if ca.shape != (self.n_rows,):
+            raise ValueError(f"centroids: expected {self.n_rows} classes, got shape {ca.shape}")
+        cen = np.empty((max(int(n_classes), 0), self.dim), np.float32)
+        cnt = np.empty(max(int(n_classes), 0), np.int64)
+        self._chk(self.lib.w2v_nn_centroids(self.x, _ptr(ca), int(n_classes), _ptr(cen), _ptr(cnt)), "w2v_nn_centroids")
+        return cen, cnt
+
+    def classes(self, n_classes: int, iterations: int = 10) -> dict:
+        """word2vec's -classes: k-means from class[r] = r mod n_classes, update then assign, `iterations` times or
+        until an iteration moves no row. Keys: classes, scores, centroids (those the classes were scored
+        against), counts (of the final classes), moved (rows moved per iteration run), iterations (run)."""
+        k, n_it = max(int(n_classes), 0), max(int(iterations), 0)
+        cls = np.empty(self.n_rows, np.int32)
+        sc = np.empty(self.n_rows, np.float32)
+        cen = np.empty((k, self.dim), np.float32)
+        cnt = np.empty(k, np.int64)
+        moved = np.zeros(n_it, np.int64)
+        run = C.c_int32()
+        self._chk(self.lib.w2v_nn_classes(self.x, int(n_classes), int(iterations), _ptr(cls), _ptr(sc), _ptr(cen),
+                                          _ptr(cnt), _ptr(moved), C.byref(run)), "w2v_nn_classes")
+        return {"classes": cls, "scores": sc, "centroids": cen, "counts": cnt, "moved": moved[:run.value],
+                "iterations": run.value}
