@@ -200,6 +200,22 @@ class Word2Vec {
   // build_vocab_file is kept for a train_file on the same file.
   bool gpu_ingest = false;
   int64_t ingest_chunk_bytes = 0;  // bytes per host -> device chunk (0 = 1 GiB)
+  // Phrases (word2phrase; include/w2v_ingest.h w2v_phrase_*): with `phrase`
+  // (the reference's member, Word2Vec.h:44, which it never reads) true,
+  // build_vocab_file ingests the file on the GPU whatever gpu_ingest says,
+  // runs one phrase pass per entry of phrase_thresholds (each with
+  // phrase_min_count) over the token ids in HBM and builds the vocabulary of
+  // the rewritten corpus: a phrase's word is left + "_" + right, composed
+  // recursively ("new_york_city" after two passes); a token of the corpus that
+  // already spells a phrase merges with it. file_samples / train_file map the
+  // same rewritten stream. Vocabulary (words, counts, tie order), samples and
+  // train_words equal what the plain path yields on the rewritten corpus
+  // written as text ("lines"); with "text8" the 1000-token sentences of the
+  // original file are kept (a re-read of a rewritten file would move the cuts).
+  // build_vocab(sentences) and train(sentences) throw while `phrase` is true:
+  // phrase mode reads files.
+  std::vector<float> phrase_thresholds = std::vector<float>(1, 100.0f);
+  int phrase_min_count = 5;
   // build_sample of a corpus file as token ids (what train_file trains on).
   void file_samples(const std::string& path, const std::string& format, int threads, std::vector<int32_t>& ids,
                     std::vector<int64_t>& offsets, int64_t& train_words);
@@ -292,6 +308,11 @@ class Word2Vec {
   std::vector<std::string> ingest_words_;  // its distinct words, in order of first occurrence
   std::vector<int64_t> ingest_counts_;
   void ingest_count(const std::string& path, const std::string& format);
+  w2v_phrase* phrases_ = nullptr;   // phrase: the rewritten stream of a file ...
+  std::string phrases_key_;         //   ... (path, format, thresholds, min count)
+  std::vector<std::string> phrase_words_;  // the word of every id of that stream (words, then phrases)
+  void phrase_run(const std::string& path, const std::string& format);
+  void drop_phrases();
 
   bool uses_C() const;
   void check_limits() const;

@@ -40,6 +40,10 @@ void w2v_model_replica_mode(w2v_model* m, int32_t mode);
 /* Word2Vec::gpu_ingest / ingest_chunk_bytes: count and map corpus files on the
  * GPU (include/w2v_ingest.h) in build_vocab_file / file_samples / train_file. */
 void w2v_model_set_gpu_ingest(w2v_model* m, int32_t on, int64_t chunk_bytes);
+/* Word2Vec::phrase / phrase_thresholds / phrase_min_count: one phrase pass
+ * (word2phrase, include/w2v_ingest.h w2v_phrase_*) per threshold before the
+ * vocabulary is built from a corpus file; n = 0 turns phrases off. */
+void w2v_model_set_phrases(w2v_model* m, const float* thresholds, int32_t n, int32_t min_count);
 
 /* Sentences as text: one per line, whitespace-separated tokens (line_docs format). */
 int w2v_model_build_vocab(w2v_model* m, const char* text, int64_t len);

@@ -186,6 +186,23 @@ SIGNATURES = {
     "w2v_ingest_samples_size": (C.c_int, [_P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64)]),
     "w2v_ingest_download": (C.c_int, [_P, _P, _P]),
     "w2v_dev_adopt_corpus": (C.c_int, [_P, _P]),
+    # phrase detection (w2v_phrase_*)
+    "w2v_phrase_create": (C.c_int, [_I32, C.POINTER(_P)]),
+    "w2v_phrase_destroy": (None, [_P]),
+    "w2v_phrase_set_table": (C.c_int, [_P, _I64]),
+    "w2v_phrase_upload": (C.c_int, [_P, _P, _I64, _P, _I64, _I64]),
+    "w2v_phrase_adopt_ingest": (C.c_int, [_P, _P]),
+    "w2v_phrase_pass": (C.c_int, [_P, _I64, _F]),
+    "w2v_phrase_summary": (C.c_int, [_P] + [C.POINTER(_I64)] * 6),
+    "w2v_phrase_times": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(_I64)]),
+    "w2v_phrase_phrases": (C.c_int, [_P, _P, _P, _P]),
+    "w2v_phrase_bigrams": (C.c_int, [_P, _P, _P, _P]),
+    "w2v_phrase_words": (C.c_int, [_P, _P, _P]),
+    "w2v_phrase_stream": (C.c_int, [_P, _P, _P]),
+    "w2v_phrase_map": (C.c_int, [_P, _P, _I64]),
+    "w2v_phrase_samples_size": (C.c_int, [_P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64)]),
+    "w2v_phrase_download": (C.c_int, [_P, _P, _P]),
+    "w2v_dev_adopt_phrases": (C.c_int, [_P, _P]),
 }
 W2V_INGEST_LINES = 0
 W2V_INGEST_TEXT8 = 1

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "Word2Vec.h"
+#include "w2v_corpus.h"
 #include "w2v_host.h"
 #include "w2v_model.h"
 
@@ -99,6 +100,29 @@ int main(int argc, char** argv) {
     int64_t tw = 0;
     b.file_samples(path, "text8", 3, ids, off, tw);
     expect(tw == 60 * 120, "train_words");
+  }
+  {  // phrase words: composed recursively from earlier ids; a bad half is refused
+    std::vector<std::string> words{"new", "york", "city"};
+    const int32_t left[2] = {0, 3}, right[2] = {1, 2};
+    w2v_corpus::append_phrase_words(words, left, right, 2);
+    expect(words.size() == 5 && words[3] == "new_york" && words[4] == "new_york_city", "phrase words");
+    const int32_t self[1] = {5}, zero[1] = {0};
+    bool threw = false;
+    try {
+      w2v_corpus::append_phrase_words(words, self, zero, 1);
+    } catch (const std::out_of_range&) {
+      threw = true;
+    }
+    expect(threw && words.size() == 5, "phrase half beyond the earlier ids rejected");
+    Word2Vec w(1, 5, 2, 20000, 16, 5, 1e-3f, 0.025f, 1e-6f, true, 1, "ns", "sg");
+    w.phrase = true;
+    threw = false;
+    try {
+      w.build_vocab(sents);
+    } catch (const std::invalid_argument&) {
+      threw = true;
+    }
+    expect(threw, "build_vocab(sentences) refused in phrase mode");
   }
   {  // C bridge argument checks
     w2v_model* m = w2v_model_new(1, 5, 2, 20000, 16, 5, 1e-3f, 0.025f, 1e-6f, 1, 1, "ns", "sg");

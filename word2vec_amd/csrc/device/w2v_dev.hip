@@ -737,12 +737,10 @@ int w2v_dev_upload_corpus(w2v_dev* h, const int32_t* ids, int64_t n_tok, const i
   return install_corpus(h, std::move(c), n_tok, n_sent, max_len, train_words, std::move(hist));
 }
 
-int w2v_dev_adopt_corpus(w2v_dev* h, w2v_ingest* g) {
-  w2v::Range range_("w2v_dev_adopt_corpus");
-  if (!h || !g) return fail(W2V_ERR_ARG, "w2v_dev_adopt_corpus: null argument");
-  const w2v::IngestView v = w2v::ingest_view(g);
-  if (!v.ok) return fail(W2V_ERR_STATE, "w2v_dev_adopt_corpus: map the ingest first");
-  if (v.device != h->device) return fail(W2V_ERR_ARG, "w2v_dev_adopt_corpus: ingest on another device");
+// Device samples (a mapped ingest's or a mapped phrase handle's) into the handle.
+static int adopt_view(w2v_dev* h, const w2v::IngestView& v, const char* what, const char* source) {
+  if (!v.ok) return fail(W2V_ERR_STATE, std::string(what) + ": map the " + source + " first");
+  if (v.device != h->device) return fail(W2V_ERR_ARG, std::string(what) + ": " + source + " on another device");
   if (h->V < 1) return fail(W2V_ERR_STATE, "upload the vocab before the corpus");
   if (v.n_vocab > h->V) return fail(W2V_ERR_ARG, "ingest vocab index beyond the handle's vocab");
   if (v.n_sentences > (int64_t)UINT32_MAX - 1) return fail(W2V_ERR_ARG, "corpus sizes out of range");
@@ -764,6 +762,18 @@ int w2v_dev_adopt_corpus(w2v_dev* h, w2v_ingest* g) {
   if (v.n_ids > 0) W2V_HIP_TRY(hipMemcpy(c->ids.get(), v.ids, v.n_ids * sizeof(int32_t), hipMemcpyDeviceToDevice));
   W2V_HIP_TRY(hipMemcpy(c->soff.get(), v.offsets, soff.size() * sizeof(int64_t), hipMemcpyDeviceToDevice));
   return install_corpus(h, std::move(c), v.n_ids, v.n_sentences, max_len, v.train_words, std::move(hist));
+}
+
+int w2v_dev_adopt_corpus(w2v_dev* h, w2v_ingest* g) {
+  w2v::Range range_("w2v_dev_adopt_corpus");
+  if (!h || !g) return fail(W2V_ERR_ARG, "w2v_dev_adopt_corpus: null argument");
+  return adopt_view(h, w2v::ingest_view(g), "w2v_dev_adopt_corpus", "ingest");
+}
+
+int w2v_dev_adopt_phrases(w2v_dev* h, w2v_phrase* p) {
+  w2v::Range range_("w2v_dev_adopt_phrases");
+  if (!h || !p) return fail(W2V_ERR_ARG, "w2v_dev_adopt_phrases: null argument");
+  return adopt_view(h, w2v::phrase_view(p), "w2v_dev_adopt_phrases", "phrase handle");
 }
 
 int w2v_dev_share_corpus(w2v_dev* h, w2v_dev* src) {

@@ -96,6 +96,8 @@ struct IngestView {
   int64_t n_vocab;
 };
 IngestView ingest_view(const w2v_ingest* g);
+// ... and of a mapped phrase handle (w2v_phrase.hip) for w2v_dev_adopt_phrases.
+IngestView phrase_view(const w2v_phrase* p);
 
 // roctx range for the duration of a scope (rocprofv3 --marker-trace shows the
 // C-ABI's uploads, epochs and replica exchanges on the timeline).

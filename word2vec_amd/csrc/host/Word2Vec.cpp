@@ -30,6 +30,7 @@ bool count_desc(Word* a, Word* b) { return a->count > b->count; }  // Word2Vec.c
 
 Word2Vec::~Word2Vec(void) {
   drop_index();
+  drop_phrases();
   if (ingest_) w2v_ingest_destroy(ingest_);
   if (dev_) w2v_dev_destroy(dev_);
 }
@@ -108,6 +109,7 @@ void Word2Vec::precalc_sampling() {
 // Word2Vec.cpp:132-169: count in corpus order with unordered_map<string,int>,
 // keep >= min_count in the map's iteration order, std::sort by count desc.
 void Word2Vec::build_vocab(std::vector<std::vector<std::string>>& sentences) {
+  if (phrase) throw std::invalid_argument("word2vec_amd: phrase mode reads files (build_vocab_file); build_vocab(sentences) does not detect phrases");
   std::unordered_map<std::string, int> tally;
   for (auto& sentence : sentences)
     for (auto& w : sentence) {
@@ -121,6 +123,22 @@ void Word2Vec::build_vocab(std::vector<std::vector<std::string>>& sentences) {
 // distinct words were first inserted, so a file's counts inserted in order of
 // first occurrence give the map build_vocab builds (corpus.cpp).
 void Word2Vec::build_vocab_file(const std::string& path, const std::string& format, int threads) {
+  if (phrase) {
+    phrase_run(path, format);
+    // the ids that still occur, in ascending order of first position: the
+    // order in which a reader of the rewritten corpus first meets the words
+    const size_t n = phrase_words_.size();
+    std::vector<int64_t> count(n), first(n);
+    check(w2v_phrase_words(phrases_, count.data(), first.data()), "w2v_phrase_words");
+    std::vector<size_t> order;
+    for (size_t k = 0; k < n; ++k)
+      if (count[k] > 0) order.push_back(k);
+    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return first[a] < first[b]; });
+    std::unordered_map<std::string, int> tally;
+    for (size_t k : order) tally[phrase_words_[k]] += (int)count[k];  // a token spelled like a phrase merges with it
+    finish_vocab(tally);
+    return;
+  }
   if (gpu_ingest) {
     ingest_count(path, format);
     std::unordered_map<std::string, int> tally;
@@ -162,8 +180,70 @@ void Word2Vec::ingest_count(const std::string& path, const std::string& format) 
   ingest_key_ = key;
 }
 
+void Word2Vec::drop_phrases() {
+  if (phrases_) w2v_phrase_destroy(phrases_);
+  phrases_ = nullptr;
+  phrases_key_.clear();
+  phrase_words_.clear();
+}
+
+// The phrase passes over a file's token ids on the GPU: count, map with the
+// identity index over all distinct words (every token stays in the stream),
+// hand the ids to a phrase handle device to device, free the ingest, run one
+// pass per threshold. Kept for a file_samples / train_file on the same file.
+void Word2Vec::phrase_run(const std::string& path, const std::string& format) {
+  std::string key = format + ":" + path + ":" + std::to_string(phrase_min_count);
+  for (float t : phrase_thresholds) key += ":" + std::to_string(t);
+  if (phrases_ && phrases_key_ == key) return;
+  drop_phrases();
+  ingest_count(path, format);
+  const size_t n_words = ingest_words_.size();
+  std::vector<int32_t> identity(n_words);
+  std::iota(identity.begin(), identity.end(), 0);
+  {
+    const w2v_corpus::File f(path);
+    check(w2v_ingest_map(ingest_, f.data(), (int64_t)f.size(), identity.data(), (int64_t)n_words), "w2v_ingest_map");
+  }
+  w2v_phrase* p = nullptr;
+  check(w2v_phrase_create(gpu_device, &p), "w2v_phrase_create");
+  phrases_ = p;
+  try {
+    check(w2v_phrase_adopt_ingest(p, ingest_), "w2v_phrase_adopt_ingest");
+    phrase_words_ = ingest_words_;
+    w2v_ingest_destroy(ingest_);
+    ingest_ = nullptr;
+    ingest_key_.clear();
+    for (float t : phrase_thresholds) check(w2v_phrase_pass(p, phrase_min_count, t), "w2v_phrase_pass");
+    int64_t total = 0, n_phrases = 0;
+    check(w2v_phrase_summary(p, &total, &n_phrases, nullptr, nullptr, nullptr, nullptr), "w2v_phrase_summary");
+    std::vector<int32_t> left((size_t)n_phrases), right((size_t)n_phrases);
+    check(w2v_phrase_phrases(p, left.data(), right.data(), nullptr), "w2v_phrase_phrases");
+    w2v_corpus::append_phrase_words(phrase_words_, left.data(), right.data(), n_phrases);
+  } catch (...) {
+    drop_phrases();
+    throw;
+  }
+  phrases_key_ = key;
+}
+
 void Word2Vec::file_samples(const std::string& path, const std::string& format, int threads,
                             std::vector<int32_t>& ids, std::vector<int64_t>& offsets, int64_t& train_words) {
+  if (phrase) {
+    phrase_run(path, format);
+    std::vector<int32_t> index(phrase_words_.size(), -1);
+    for (size_t k = 0; k < phrase_words_.size(); ++k) {
+      auto it = vocab_hash.find(phrase_words_[k]);
+      if (it != vocab_hash.end()) index[k] = (int32_t)it->second->index;
+    }
+    check(w2v_phrase_map(phrases_, index.data(), (int64_t)index.size()), "w2v_phrase_map");
+    int64_t n_ids = 0, n_sent = 0;
+    check(w2v_phrase_samples_size(phrases_, &n_ids, &n_sent, &train_words), "w2v_phrase_samples_size");
+    ids.resize((size_t)n_ids);
+    offsets.resize((size_t)n_sent + 1);
+    check(w2v_phrase_download(phrases_, ids.data(), offsets.data()), "w2v_phrase_download");
+    drop_phrases();  // as the ingest below: the device memory goes before training uploads
+    return;
+  }
   if (gpu_ingest) {
     ingest_count(path, format);
     std::vector<int32_t> index(ingest_words_.size(), -1);
@@ -696,6 +776,7 @@ void Word2Vec::check_limits() const {
 
 // Word2Vec.cpp:356-396.
 void Word2Vec::train(std::vector<std::vector<std::string>>& sentences) {
+  if (phrase) throw std::invalid_argument("word2vec_amd: phrase mode reads files (train_file); train(sentences) does not detect phrases");
   check_limits();
   drop_index();
   if (!resume_) init_weights(vocab.size());

@@ -297,4 +297,13 @@ Samples samples(const File& f, Format fmt, int threads, const std::unordered_map
   return out;
 }
 
+void append_phrase_words(std::vector<std::string>& words, const int32_t* left, const int32_t* right, int64_t n) {
+  for (int64_t j = 0; j < n; ++j) {
+    const size_t have = words.size();
+    if (left[j] < 0 || right[j] < 0 || (size_t)left[j] >= have || (size_t)right[j] >= have)
+      throw std::out_of_range("phrase " + std::to_string(j) + " refers to an id that is not before it");
+    words.push_back(words[(size_t)left[j]] + "_" + words[(size_t)right[j]]);
+  }
+}
+
 }  // namespace w2v_corpus

@@ -8,7 +8,9 @@
 // is written (:196-201). Additive: -train is honoured (the reference always
 // reads ./text8), -binary, -gpu, -replay, -shared-negatives, and the
 // multi-GPU flags -gpus, -sync-words, -overlap, -replica-mode (Word2Vec::gpu_devices), -gpu-ingest,
-// and -classes (in the reference's help text, never parsed by its main).
+// -classes (in the reference's help text, never parsed by its main), and
+// -phrase / -phrase-min-count (word2phrase passes before the vocabulary).
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -49,7 +51,10 @@ void usage() {
                "                        (default auto: average for <= 4 replicas of >= 256 M words each, else sum for 2, adaptive for more)\n"
                "  -gpu-ingest <0|1>     count and map the corpus on the GPU (default 0: host threads)\n"
                "  -classes <int>        output word classes rather than word vectors: k-means over the vectors on the\n"
-               "                        GPU, one \"word class\" line per word (default 0: vectors are written)\n\n"
+               "                        GPU, one \"word class\" line per word (default 0: vectors are written)\n"
+               "  -phrase <t1[,t2...]>  join word pairs into phrases (new_york) on the GPU before training: one word2phrase\n"
+               "                        pass per comma-separated threshold >= 0, e.g. 200,100 (default: off)\n"
+               "  -phrase-min-count <int> words and pairs rarer than this never join (default 5)\n\n"
                "example: ./word2vec -train text8 -output vec.txt -size 300 -window 5 -subsample 1e-4 "
                "-negative 5 -model sg -train_method ns -iter 3\n";
 }
@@ -107,6 +112,27 @@ int main(int argc, char** argv) {
   if ((i = find_flag("-replica-mode", argc, argv)) > 0) replica_mode = argv[i + 1];
   if ((i = find_flag("-gpu-ingest", argc, argv)) > 0) gpu_ingest = std::atoi(argv[i + 1]);
   if ((i = find_flag("-classes", argc, argv)) > 0) classes = std::atoi(argv[i + 1]);
+  std::vector<float> phrase_thresholds;
+  int phrase_min_count = 5;
+  bool phrase_ok = true;
+  if ((i = find_flag("-phrase", argc, argv)) > 0) {
+    const std::string list = argv[i + 1];
+    size_t b = 0;
+    while (b <= list.size()) {  // comma-separated, every piece a finite float >= 0
+      const size_t e = std::min(list.find(',', b), list.size());
+      const std::string piece = list.substr(b, e - b);
+      char* end = nullptr;
+      const float t = std::strtof(piece.c_str(), &end);
+      if (piece.empty() || *end != '\0' || !(t >= 0.0f) || t > 3.0e38f) phrase_ok = false;
+      phrase_thresholds.push_back(t);
+      b = e + 1;
+    }
+  }
+  if ((i = find_flag("-phrase-min-count", argc, argv)) > 0) phrase_min_count = std::atoi(argv[i + 1]);
+  if (!phrase_ok || phrase_min_count < 1) {
+    std::cout << "Please set -phrase to comma-separated thresholds >= 0 and -phrase-min-count >= 1!" << std::endl;
+    return 1;
+  }
   if (classes < 0) {
     std::cout << "Please set -classes >= 0!" << std::endl;
     return 1;
@@ -182,6 +208,11 @@ int main(int argc, char** argv) {
   w2v.overlap_average = overlap != 0;
   w2v.replica_mode = replica_mode_id;
   w2v.gpu_ingest = gpu_ingest != 0;
+  if (!phrase_thresholds.empty()) {
+    w2v.phrase = true;
+    w2v.phrase_thresholds = phrase_thresholds;
+    w2v.phrase_min_count = phrase_min_count;
+  }
   // main.cpp:63-92's reader (1000-token sentences), streamed from the mapped
   // file by host threads: the same vocabulary and samples as building
   // vector<vector<string>> first (Word2Vec::build_vocab_file / train_file)

@@ -109,6 +109,12 @@ void w2v_model_set_gpu_ingest(w2v_model* m, int32_t on, int64_t chunk_bytes) {
   m->w.ingest_chunk_bytes = chunk_bytes > 0 ? chunk_bytes : 0;
 }
 
+void w2v_model_set_phrases(w2v_model* m, const float* thresholds, int32_t n, int32_t min_count) {
+  m->w.phrase = n > 0 && thresholds;
+  if (m->w.phrase) m->w.phrase_thresholds.assign(thresholds, thresholds + n);
+  m->w.phrase_min_count = min_count;
+}
+
 int w2v_model_build_vocab(w2v_model* m, const char* text, int64_t len) {
   return guard(m, [&] {
     auto s = parse(text, len);

@@ -50,6 +50,11 @@ struct Samples {
 // build_sample over the file with `index` (word -> vocab index).
 Samples samples(const File& f, Format fmt, int threads, const std::unordered_map<std::string, int32_t>& index);
 
+// Phrase words: words holds the word of every id so far; phrase j (its halves
+// are earlier ids: words or earlier phrases) appends words[left[j]] + "_" +
+// words[right[j]]. Throws std::out_of_range for a half that is not an earlier id.
+void append_phrase_words(std::vector<std::string>& words, const int32_t* left, const int32_t* right, int64_t n);
+
 }  // namespace w2v_corpus
 
 #endif  // W2V_AMD_CORPUS_H

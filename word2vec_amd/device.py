@@ -157,6 +157,14 @@ class DeviceTrainer:
                   "w2v_ingest_samples_size")
         self.n_sent = ns.value
 
+    def adopt_phrases(self, phrases):
+        """w2v_dev_adopt_phrases: the samples of a mapped GpuPhrases (word2vec_amd/phrases.py), device to device."""
+        self._chk(self.lib.w2v_dev_adopt_phrases(self.h, phrases.p), "w2v_dev_adopt_phrases")
+        ni, ns, tw = C.c_int64(), C.c_int64(), C.c_int64()
+        self._chk(self.lib.w2v_phrase_samples_size(phrases.p, C.byref(ni), C.byref(ns), C.byref(tw)),
+                  "w2v_phrase_samples_size")
+        self.n_sent = ns.value
+
     def upload_replay(self, stream, offsets):
         s = np.ascontiguousarray(stream, dtype=np.uint32)
         o = np.ascontiguousarray(offsets, dtype=np.int64)

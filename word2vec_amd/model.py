@@ -37,6 +37,7 @@ def _load():
             "w2v_model_replicas": (None, [P, P, I32, I64, I32]),
             "w2v_model_replica_mode": (None, [P, I32]),
             "w2v_model_set_gpu_ingest": (None, [P, I32, I64]),
+            "w2v_model_set_phrases": (None, [P, P, I32, I32]),
             "w2v_model_build_vocab": (C.c_int, [P, S, I64]),
             "w2v_model_train": (C.c_int, [P, S, I64]),
             "w2v_model_train_ids": (C.c_int, [P, P, P, I64, I64]),
@@ -104,7 +105,8 @@ class Word2Vec:
                  train_method="hs", model="cbow", gpu_device=0, replay_rng=False, verbose=False, hot_rows=-2,
                  private_rows=-1, flush_centers=0, private_average=8.0, max_waves=0, shared_negatives=False,
                  context_rows=-1, context_flush=0, gpu_devices=None, sync_words=0, overlap_average=True,
-                 replica_mode="auto", gpu_ingest=False, ingest_chunk_bytes=0, checkpoint_path=""):
+                 replica_mode="auto", gpu_ingest=False, ingest_chunk_bytes=0, checkpoint_path="",
+                 phrase_thresholds=None, phrase_min_count=5):
         self.L = _load()
         self.word_dim = word_dim
         self.h = self.L.w2v_model_new(iter, window, min_count, table_size, word_dim, negative, subsample_threshold,
@@ -122,6 +124,10 @@ class Word2Vec:
             self.L.w2v_model_replicas(self.h, _p(devs), devs.size, int(sync_words), int(bool(overlap_average)))
             self.L.w2v_model_replica_mode(self.h, REPLICA_MODES.get(replica_mode, replica_mode))
         self.L.w2v_model_set_gpu_ingest(self.h, int(bool(gpu_ingest)), int(ingest_chunk_bytes))
+        if phrase_thresholds is not None and len(phrase_thresholds) > 0:
+            # Word2Vec::phrase: one word2phrase pass per threshold over the file's ids on the GPU
+            t = np.ascontiguousarray(phrase_thresholds, np.float32)
+            self.L.w2v_model_set_phrases(self.h, _p(t), t.size, int(phrase_min_count))
         if checkpoint_path:
             self.set_checkpoint_path(checkpoint_path)
 
