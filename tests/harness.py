@@ -58,6 +58,40 @@ def device_from_oracle(o: Oracle, cfg, initial=True):
     return d
 
 
+def bound_device_from_oracle(o: Oracle, cfg, pitch=None, extra=64):
+    """device_from_oracle(initial=False) on caller-owned matrices, bench.py's
+    path: W / C / synapses1 are zero-initialised torch tensors of row pitch
+    `pitch` floats (default: the kernels' row width + `extra`), their
+    [:rows, :dim] blocks filled from the oracle's current matrices and handed
+    to bind_model. Returns (trainer, [W, C, S] tensors or None, pitch)."""
+    import torch
+
+    from word2vec_amd.device import DeviceTrainer
+
+    d = DeviceTrainer(cfg)
+    codes = points = off = None
+    if cfg.hs:
+        codes, points, off = o.huffman()
+    d.upload_vocab(o.sample_probs(), o.table_bounds() if cfg.negative > 0 else None, codes, points, off)
+    if pitch is None:
+        pitch = d.row_pitch() + extra
+    have = (True, cfg.negative > 0 or cfg.cbow, cfg.hs)
+    tens = []
+    for k in range(3):
+        if not have[k]:
+            tens.append(None)
+            continue
+        m = o.matrix(k)
+        t = torch.zeros(m.shape[0], pitch, dtype=torch.float32, device="cuda")
+        t[:, :cfg.word_dim] = torch.from_numpy(m).to(t.device)
+        tens.append(t)
+    torch.cuda.synchronize()  # the handle trains on a stream of its own
+    d.bind_model(*[t.data_ptr() if t is not None else None for t in tens], pitch)
+    ids, soff = o.samples()
+    d.upload_corpus(ids, soff, o.train_words)
+    return d, tens, pitch
+
+
 def rel_err(a, b):
     """Norm-wise: max |a - b| over the whole matrix / max |b| (a matrix-level bound)."""
     a = np.asarray(a, np.float64)
