@@ -109,6 +109,37 @@ def test_gpu_ingest_empty_and_whitespace_only(tmp_path):
             _both(p, fmt, min_count=1)
 
 
+def _write_many_words(path, n_distinct=40_000, seed=11):
+    """n_distinct words w0, w1, ..., each 1 to 4 times, shuffled, 40 tokens per line; returns the tokens."""
+    rng = np.random.default_rng(seed)
+    toks = np.repeat(np.arange(n_distinct), rng.integers(1, 5, n_distinct))
+    rng.shuffle(toks)
+    words = [f"w{t}" for t in toks]
+    path.write_text("".join(" ".join(words[i:i + 40]) + "\n" for i in range(0, len(words), 40)))
+    return words
+
+
+def test_gpu_ingest_table_growth(tmp_path):
+    """The word table doubles in mid-file. A file under 4 MiB starts it at 2^16
+    slots; more than 2^15 distinct words fill it past half, so it grows once,
+    to 2^17. With 4 KiB chunks that happens after well over a hundred chunks
+    were counted: the rehash has to carry every word's count, first offset,
+    second hash and length into the new table (a lost count or first offset
+    changes the vocabulary, whose order among the four counts is all ties,
+    decided by first occurrence; a lost hash or length fails the map). Each
+    workgroup of the count kernel also sees about as many distinct slots as
+    its LDS table has entries, so slots that find no entry within the probe
+    limit take the direct add to HBM."""
+    path = tmp_path / "many.txt"
+    words = _write_many_words(path)
+    assert len(set(words)) > 32_768          # past half of 2^16 slots
+    assert path.stat().st_size // 64 < 1 << 16  # the automatic table starts at its smallest
+    for fmt in ("lines", "text8"):
+        for chunk in (0, 4096):
+            ids, off, tw = _both(path, fmt, chunk, min_count=1)
+            assert tw == ids.size == len(words)
+
+
 @pytest.mark.parametrize("resident", [-1, 0])
 def test_gpu_ingest_python_wrapper_and_adopt(tmp_path, resident):
     """GpuIngest.count() returns the words in order of first occurrence with

@@ -29,6 +29,9 @@
 //     position, and the token that opens sentence s writes offsets[s] (text8:
 //     raw token index 1000 s; lines: the first token of a line, which also
 //     writes the offsets of the empty lines before it).
+// The table's probe loops, the count kernel, the ordering of the used slots and
+// the growth step are w2v_table.hpp's, shared with w2v_phrase.hip; the columns,
+// the key, insert_kernel and the payload-moving rehash_kernel are this unit's.
 // The per-word token histogram the training handle needs (flush scales,
 // w2v_dev_adopt_corpus) is the vocab words' counts from pass 1.
 // The work is byte- and hash-table-bound, far from the HBM roofline: the
@@ -43,16 +46,15 @@
 
 #include "w2v_dev_internal.hpp"
 #include "w2v_ingest.h"
+#include "w2v_table.hpp"
 
 namespace w2v {
 namespace ingest {
 
-constexpr uint64_t kEmpty = 0;
+using namespace w2v::table;
+
 constexpr int64_t kText8Sentence = 1000;  // main.cpp:66
 constexpr int kMaxProbe = 4096;           // a longer chain counts as a full table (the table grows)
-constexpr int kBlock = 256;
-constexpr int kLdsSlots = 4096;  // per-workgroup count aggregation
-constexpr uint32_t kLdsEmpty = 0xFFFFFFFFu;
 constexpr int64_t kResidentMax = (int64_t)64 << 30;  // default: bytes of corpus kept in HBM between the passes
 
 __device__ __forceinline__ bool is_space(unsigned char c) {  // C-locale isspace, as operator>>
@@ -118,12 +120,6 @@ __global__ __launch_bounds__(256) void tile_write_kernel(const unsigned char* b,
   }
 }
 
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {  // splitmix64 finaliser
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
 // One token: its length, two hashes, and the newlines before the next token.
 struct Tok {
   uint32_t len;
@@ -164,27 +160,8 @@ struct Table {
   uint64_t mask;
 };
 
-// Claim (CAS) or find key h1 from its home slot; -1 after kMaxProbe slots.
-__device__ __forceinline__ int64_t claim(const Table& tab, uint64_t h1, bool* won) {
-  uint64_t i = h1 & tab.mask;
-  *won = false;
-  for (int probe = 0; probe < kMaxProbe; ++probe, i = (i + 1) & tab.mask) {
-    uint64_t cur = __hip_atomic_load(&tab.key[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (cur == kEmpty) {
-      uint64_t expected = kEmpty;
-      if (__hip_atomic_compare_exchange_strong(&tab.key[i], &expected, h1, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                               __HIP_MEMORY_SCOPE_AGENT)) {
-        *won = true;
-        return (int64_t)i;
-      }
-      cur = expected;
-    }
-    if (cur == h1) return (int64_t)i;
-  }
-  return -1;
-}
-
 // Pass 1, insert (idempotent). base_off: the chunk's byte offset in the file.
+// The key is the first hash, already mixed: its home slot is h1 & mask.
 __global__ void insert_kernel(const unsigned char* b, int64_t n, const int64_t* starts, int64_t nt, int64_t base_off,
                               Table tab, uint32_t* slot, uint32_t* nl_after, unsigned long long* used,
                               unsigned long long* fail) {
@@ -194,9 +171,10 @@ __global__ void insert_kernel(const unsigned char* b, int64_t n, const int64_t* 
     const Tok k = read_token(b, n, s);
     nl_after[t] = k.nl_after;
     bool won = false;
-    const int64_t i = claim(tab, k.h1, &won);
+    const int64_t i = claim<kMaxProbe>(tab.key, tab.mask, k.h1 & tab.mask, k.h1, &won);
     if (i < 0) {
       atomicAdd(fail, 1ull);
+      slot[t] = kNone;
       continue;
     }
     if (won) {
@@ -217,7 +195,7 @@ __global__ void rehash_kernel(Table from, int64_t from_cap, Table to, unsigned l
     const uint64_t h1 = from.key[i];
     if (h1 == kEmpty) continue;
     bool won = false;
-    const int64_t j = claim(to, h1, &won);
+    const int64_t j = claim<kMaxProbe>(to.key, to.mask, h1 & to.mask, h1, &won);
     if (j < 0 || !won) {
       atomicAdd(fail, 1ull);
       continue;
@@ -227,51 +205,6 @@ __global__ void rehash_kernel(Table from, int64_t from_cap, Table to, unsigned l
     to.first[j] = from.first[i];
     to.count[j] = from.count[i];
   }
-}
-
-// Pass 1, count: per workgroup, adds go to an LDS table of slots first; a
-// slot that finds no LDS entry within 8 probes adds to HBM directly.
-__global__ __launch_bounds__(kBlock) void count_kernel(const uint32_t* slot, int64_t nt, unsigned long long* count) {
-  __shared__ uint32_t lkey[kLdsSlots];
-  __shared__ uint32_t lcnt[kLdsSlots];
-  for (int h = threadIdx.x; h < kLdsSlots; h += kBlock) {
-    lkey[h] = kLdsEmpty;
-    lcnt[h] = 0;
-  }
-  __syncthreads();
-  const int64_t per = (nt + gridDim.x - 1) / gridDim.x;
-  const int64_t lo = (int64_t)blockIdx.x * per, hi = min(nt, lo + per);
-  for (int64_t t = lo + threadIdx.x; t < hi; t += kBlock) {
-    const uint32_t s = slot[t];
-    uint32_t h = (s * 2654435761u) >> 20;  // 12 bits
-    bool done = false;
-    for (int probe = 0; probe < 8 && !done; ++probe, h = (h + 1) & (kLdsSlots - 1)) {
-      uint32_t k = lkey[h];
-      if (k == kLdsEmpty) {
-        const uint32_t old = atomicCAS(&lkey[h], kLdsEmpty, s);
-        k = old == kLdsEmpty ? s : old;  // claimed it, or another thread did
-      }
-      if (k == s) {
-        atomicAdd(&lcnt[h], 1u);
-        done = true;
-      }
-    }
-    if (!done) atomicAdd(&count[s], 1ull);
-  }
-  __syncthreads();
-  for (int h = threadIdx.x; h < kLdsSlots; h += kBlock)
-    if (lcnt[h]) atomicAdd(&count[lkey[h]], (unsigned long long)lcnt[h]);
-}
-
-struct UsedSlot {
-  const uint64_t* key;
-  __host__ __device__ bool operator()(const int64_t& i) const { return key[i] != kEmpty; }
-};
-
-__global__ void gather_first_kernel(const int64_t* slots, int64_t m, const unsigned long long* first,
-                                    unsigned long long* out) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < m; k += stride) out[k] = first[slots[k]];
 }
 
 __global__ void gather_words_kernel(const int64_t* order, int64_t m, Table tab, int64_t* first, int32_t* len,
@@ -298,20 +231,14 @@ __global__ void map_kernel(const unsigned char* b, int64_t n, const int64_t* sta
   for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < nt; t += stride) {
     const Tok k = read_token(b, n, starts[t]);
     nl_after[t] = k.nl_after;
-    uint64_t i = k.h1 & tab.mask;
+    const int64_t i = find(tab.key, tab.mask, k.h1 & tab.mask, k.h1);
     int32_t id = -1;
-    bool found = false;
-    for (uint64_t probe = 0; probe <= tab.mask; ++probe, i = (i + 1) & tab.mask) {
-      const uint64_t cur = tab.key[i];
-      if (cur == kEmpty) break;
-      if (cur == k.h1) {
-        found = true;
-        if (tab.h2[i] != k.h2 || tab.len[i] != k.len) atomicAdd(mismatch, 1ull);
-        id = slot_id[i];
-        break;
-      }
+    if (i < 0) {
+      atomicAdd(mismatch, 1ull);  // pass 2 saw a word pass 1 did not (different bytes)
+    } else {
+      if (tab.h2[i] != k.h2 || tab.len[i] != k.len) atomicAdd(mismatch, 1ull);
+      id = slot_id[i];
     }
-    if (!found) atomicAdd(mismatch, 1ull);  // pass 2 saw a word pass 1 did not (different bytes)
     tok_id[t] = id;
     kept[t] = id >= 0 ? 1 : 0;
   }
@@ -346,14 +273,6 @@ __global__ void add_base_kernel(int64_t* l, int64_t m, int64_t base) {
   for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < m; t += stride) l[t] += base;
 }
 
-struct NotNegative {
-  __host__ __device__ bool operator()(const int32_t& v) const { return v >= 0; }
-};
-
-inline dim3 grid_for(int64_t n) {
-  return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(8192, (n + kBlock - 1) / kBlock)));
-}
-
 }  // namespace ingest
 }  // namespace w2v
 
@@ -368,6 +287,20 @@ struct TableBuf {
   DevBuf<uint32_t> len;
   int64_t cap() const { return (int64_t)key.size(); }
   Table view() const { return Table{key.get(), h2.get(), first.get(), count.get(), len.get(), (uint64_t)cap() - 1}; }
+  // Becomes an empty table of `cap` slots (a power of two).
+  int alloc(int64_t cap, hipStream_t s) {
+    TableBuf t;
+    const size_t n = (size_t)cap;
+    int rc;
+    if ((rc = t.key.alloc(n)) || (rc = t.h2.alloc(n)) || (rc = t.first.alloc(n)) || (rc = t.count.alloc(n)) ||
+        (rc = t.len.alloc(n)))
+      return rc;
+    W2V_HIP_TRY(hipMemsetAsync(t.key.get(), 0, n * sizeof(uint64_t), s));
+    W2V_HIP_TRY(hipMemsetAsync(t.first.get(), 0xFF, n * sizeof(unsigned long long), s));
+    W2V_HIP_TRY(hipMemsetAsync(t.count.get(), 0, n * sizeof(unsigned long long), s));
+    *this = std::move(t);
+    return W2V_OK;
+  }
 };
 
 // The chunk work buffers, sized together (ensure_work).
@@ -434,40 +367,15 @@ std::vector<std::pair<int64_t, int64_t>> chunks(const char* p, int64_t n, int64_
   return r;
 }
 
-// An empty table of `cap` slots (a power of two) into `out`.
-int alloc_table(TableBuf& out, int64_t cap, hipStream_t s) {
-  TableBuf t;
-  const size_t n = (size_t)cap;
-  int rc;
-  if ((rc = t.key.alloc(n)) || (rc = t.h2.alloc(n)) || (rc = t.first.alloc(n)) || (rc = t.count.alloc(n)) ||
-      (rc = t.len.alloc(n)))
-    return rc;
-  W2V_HIP_TRY(hipMemsetAsync(t.key.get(), 0, n * sizeof(uint64_t), s));
-  W2V_HIP_TRY(hipMemsetAsync(t.first.get(), 0xFF, n * sizeof(unsigned long long), s));
-  W2V_HIP_TRY(hipMemsetAsync(t.count.get(), 0, n * sizeof(unsigned long long), s));
-  out = std::move(t);
-  return W2V_OK;
-}
-
-constexpr int64_t kMaxCap = (int64_t)1 << 30;
-
-// Double the table until it holds `need` words at most half full.
-int grow(w2v_ingest* g, int64_t need) {
-  int64_t cap = g->tab.cap() * 2;
-  while (cap < 2 * need) cap <<= 1;
-  if (cap > kMaxCap) return w2v::set_error(W2V_ERR_UNSUPPORTED, "w2v_ingest_count: more than 2^29 distinct words");
-  TableBuf nt;
-  if (int rc = alloc_table(nt, cap, g->stream)) return rc;
-  W2V_HIP_TRY(hipMemsetAsync(g->ctr.get() + 1, 0, sizeof(unsigned long long), g->stream));
-  hipLaunchKernelGGL(rehash_kernel, grid_for(g->tab.cap()), dim3(kBlock), 0, g->stream, g->tab.view(), g->tab.cap(),
-                     nt.view(), g->ctr.get() + 1);
-  W2V_HIP_TRY(hipGetLastError());
-  unsigned long long f = 0;
-  W2V_HIP_TRY(hipMemcpyAsync(&f, g->ctr.get() + 1, sizeof(f), hipMemcpyDeviceToHost, g->stream));
-  W2V_HIP_TRY(hipStreamSynchronize(g->stream));
-  g->tab = std::move(nt);
-  if (f) return w2v::set_error(W2V_ERR_STATE, "w2v_ingest_count: rehash lost words");
-  return W2V_OK;
+// Double the table until it holds `need` words at most half full; the rehash carries the words' payload.
+int grow_words(w2v_ingest* g, int64_t need) {
+  unsigned long long* fail = g->ctr.get() + 1;
+  auto rehash = [&](const TableBuf& from, const TableBuf& to) {
+    hipLaunchKernelGGL(rehash_kernel, grid_for(from.cap()), dim3(kBlock), 0, g->stream, from.view(), from.cap(),
+                       to.view(), fail);
+  };
+  return grow(g->stream, g->tab, need, fail, rehash, "w2v_ingest_count: more than 2^29 distinct words",
+              "w2v_ingest_count: rehash lost words");
 }
 
 // hipcub's element counts are int: a chunk is at most INT32_MAX - 64 bytes
@@ -555,37 +463,13 @@ int64_t chunk_size_limit(const w2v_ingest* g) { return std::min<int64_t>(g->chun
 
 // The used slots sorted by first occurrence -> g->order.
 int order_words(w2v_ingest* g, int64_t n_words) {
-  DevBuf<int64_t> order, slots;
-  DevBuf<unsigned long long> firsts, firsts_sorted;
-  DevBuf<unsigned char> tmp;
-  int rc;
-  if ((rc = order.alloc((size_t)std::max<int64_t>(n_words, 1)))) return rc;
-  if (n_words > 0) {
-    const size_t m = (size_t)n_words;
-    const int cap = (int)g->tab.cap();
-    int64_t* n_sel = g->w.n_sel.get();
-    if ((rc = slots.alloc(m)) || (rc = firsts.alloc(m)) || (rc = firsts_sorted.alloc(m))) return rc;
-    hipcub::CountingInputIterator<int64_t> it(0);
-    const UsedSlot used{g->tab.key.get()};
-    size_t t1 = 0, t2 = 0;
-    W2V_HIP_TRY(hipcub::DeviceSelect::If(nullptr, t1, it, slots.get(), n_sel, cap, used, g->stream));
-    W2V_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, t2, firsts.get(), firsts_sorted.get(), slots.get(),
-                                                   order.get(), (int)n_words, 0, 64, g->stream));
-    if ((rc = tmp.alloc(std::max<size_t>(std::max(t1, t2), 1)))) return rc;
-    size_t t = tmp.size();
-    W2V_HIP_TRY(hipcub::DeviceSelect::If(tmp.get(), t, it, slots.get(), n_sel, cap, used, g->stream));
-    int64_t sel = 0;
-    W2V_HIP_TRY(hipMemcpyAsync(&sel, n_sel, sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
-    W2V_HIP_TRY(hipStreamSynchronize(g->stream));
-    if (sel != n_words) return w2v::set_error(W2V_ERR_STATE, "w2v_ingest_count: used-slot count mismatch");
-    hipLaunchKernelGGL(gather_first_kernel, grid_for(n_words), dim3(kBlock), 0, g->stream, slots.get(), n_words,
-                       g->tab.first.get(), firsts.get());
-    W2V_HIP_TRY(hipGetLastError());
-    t = tmp.size();
-    W2V_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.get(), t, firsts.get(), firsts_sorted.get(), slots.get(),
-                                                   order.get(), (int)n_words, 0, 64, g->stream));
-    W2V_HIP_TRY(hipStreamSynchronize(g->stream));
-  }
+  DevBuf<int64_t> order;
+  DevBuf<unsigned long long> firsts_sorted;
+  int64_t sel = 0;
+  if (int rc = select_sorted(g->stream, g->tab.cap(), Used{g->tab.key.get()}, g->tab.first.get(), order, firsts_sorted,
+                             &sel))
+    return rc;
+  if (sel != n_words) return w2v::set_error(W2V_ERR_STATE, "w2v_ingest_count: used-slot count mismatch");
   g->order = std::move(order);
   return W2V_OK;
 }
@@ -674,7 +558,7 @@ int w2v_ingest_count(w2v_ingest* g, const char* data, int64_t n) {
   // the table starts at 2^16..2^24 slots and doubles whenever it is half full
   int64_t cap = (int64_t)1 << 16;
   while (cap < std::min<int64_t>(n / 64, (int64_t)1 << 24)) cap <<= 1;
-  if (int rc = alloc_table(g->tab, cap, g->stream)) return rc;
+  if (int rc = g->tab.alloc(cap, g->stream)) return rc;
   W2V_HIP_TRY(hipMemsetAsync(g->ctr.get(), 0, 3 * sizeof(unsigned long long), g->stream));
   int64_t raw = 0, newlines = 0;
   for (auto& c : cs) {
@@ -692,10 +576,10 @@ int w2v_ingest_count(w2v_ingest* g, const char* data, int64_t n) {
         W2V_HIP_TRY(hipMemcpyAsync(cnt, g->ctr.get(), sizeof(cnt), hipMemcpyDeviceToHost, g->stream));
         W2V_HIP_TRY(hipStreamSynchronize(g->stream));
         if (cnt[1] == 0 && (int64_t)cnt[0] * 2 <= g->tab.cap()) break;
-        if (int rc = grow(g, (int64_t)cnt[0] + (int64_t)cnt[1])) return rc;
+        if (int rc = grow_words(g, (int64_t)cnt[0] + (int64_t)cnt[1])) return rc;
       }
-      hipLaunchKernelGGL(count_kernel, grid_for(nt / 16), dim3(kBlock), 0, g->stream, g->w.slot.get(), nt,
-                         g->tab.count.get());
+      hipLaunchKernelGGL(count_kernel<false>, grid_for(nt / 16), dim3(kBlock), 0, g->stream, g->w.slot.get(), nt,
+                         g->tab.count.get(), (ull*)nullptr);
       W2V_HIP_TRY(hipGetLastError());
       int64_t last_line = 0, after = 0;
       if (int rc = lines_of(g, nt, 0, &last_line, &after)) return rc;
@@ -744,15 +628,9 @@ int w2v_ingest_map(w2v_ingest* g, const char* data, int64_t n, const int32_t* vo
   w2v::Range range_("w2v_ingest_map");
   W2V_HIP_TRY(hipSetDevice(g->device));
   g->mapped = false;
-  int32_t vmax = -1;
-  for (int64_t k = 0; k < n_words; ++k) {
-    if (vocab_index[k] < -1) return w2v::set_error(W2V_ERR_ARG, "vocab_index entries must be >= -1");
-    vmax = std::max(vmax, vocab_index[k]);
-  }
-  // per-id token histogram: every occurrence of an in-vocab word is kept
-  std::vector<int64_t> hist((size_t)vmax + 1, 0);
-  for (int64_t k = 0; k < n_words; ++k)
-    if (vocab_index[k] >= 0) hist[(size_t)vocab_index[k]] += g->word_count[(size_t)k];
+  std::vector<int64_t> hist;  // tokens per vocab id, from pass 1's counts
+  if (!vocab_hist(vocab_index, g->word_count.data(), n_words, hist))
+    return w2v::set_error(W2V_ERR_ARG, "vocab_index entries must be >= -1");
   // slot -> vocab index
   DevBuf<int32_t> d_slot, d_vidx, ids;
   DevBuf<int64_t> offsets;
@@ -787,18 +665,15 @@ int w2v_ingest_map(w2v_ingest* g, const char* data, int64_t n, const int32_t* vo
       W2V_HIP_TRY(hipGetLastError());
       int64_t last_line = 0, after = 0;
       if ((rc = lines_of(g, nt, line_base, &last_line, &after))) return rc;
-      size_t tb = w.temp.size();
-      W2V_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(w.temp.get(), tb, w.kept.get(), w.kpos.get(), (int)nt, g->stream));
+      int64_t sel = 0;  // the chunk's in-vocab tokens (w.temp holds the scan's scratch at the largest size: ensure_work)
+      if ((rc = exclusive_sum(g->stream, w.kept.get(), w.kpos.get(), nt, &sel, w.temp))) return rc;
       hipLaunchKernelGGL(boundary_kernel, grid_for(nt), dim3(kBlock), 0, g->stream, w.kpos.get(), w.line_of.get(), nt,
                          raw, kept, prev_line, lines ? 0 : 1, offsets.get());
       W2V_HIP_TRY(hipGetLastError());
       // append the chunk's in-vocab ids
-      tb = w.temp.size();
+      size_t tb = w.temp.size();
       W2V_HIP_TRY(hipcub::DeviceSelect::If(w.temp.get(), tb, w.tok_id.get(), ids.get() + kept, w.n_sel.get(), (int)nt,
                                            NotNegative(), g->stream));
-      int64_t sel = 0;
-      W2V_HIP_TRY(hipMemcpyAsync(&sel, w.n_sel.get(), sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
-      W2V_HIP_TRY(hipStreamSynchronize(g->stream));
       kept += sel;
       prev_line = last_line;
       line_base = last_line + after;

@@ -30,6 +30,8 @@
 //     on the launch. offsets'[s] = outpos[offsets[s]] (a sentence start is
 //     never joined);
 //   * the new stream's histogram.
+// The probe loop, count_kernel, the select + sort and the growth step are
+// w2v_table.hpp's, shared with w2v_ingest.hip.
 // Only integer atomics (compare-and-swap, add, min). hipcub's element counts
 // are int: a stream holds fewer than 2^31 - 64 tokens and the table at most
 // 2^30 slots.
@@ -44,27 +46,17 @@
 
 #include "w2v_dev_internal.hpp"
 #include "w2v_ingest.h"
+#include "w2v_table.hpp"
 
 namespace w2v {
 namespace phrase {
 
-using ull = unsigned long long;
+using namespace w2v::table;  // kNone: slot[i] of a position that holds no eligible pair
 
-constexpr uint64_t kEmpty = 0;
-constexpr uint32_t kNone = 0xFFFFFFFFu;  // slot[i] of a position that holds no eligible pair
-constexpr ull kNever = ~0ull;            // first / firstjoin of a word / pair never seen / joined
-constexpr int kMaxProbe = 512;           // a longer chain counts as a full table (the table grows)
-constexpr int kBlock = 256;
-constexpr int kLdsSlots = 4096;  // per-workgroup count aggregation
+constexpr ull kNever = ~0ull;   // first / firstjoin of a word / pair never seen / joined
+constexpr int kMaxProbe = 512;  // a longer chain counts as a full table (the table grows)
 constexpr int64_t kMaxTokens = (int64_t)INT32_MAX - 64;
-constexpr int64_t kMaxCap = (int64_t)1 << 30;
 constexpr int64_t kMaxWords = (int64_t)1 << 31;
-
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {  // splitmix64 finaliser
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 
 struct Table {
   uint64_t* key;   // (a << 32 | b) + 1, 0 = empty
@@ -75,26 +67,6 @@ struct Table {
   uint64_t mask;
 };
 
-// Claim (CAS) or find `key` from its home slot; -1 after kMaxProbe slots.
-__device__ __forceinline__ int64_t claim(const Table& tab, uint64_t key, bool* won) {
-  uint64_t i = mix64(key) & tab.mask;
-  *won = false;
-  for (uint64_t probe = 0; probe < (uint64_t)kMaxProbe && probe <= tab.mask; ++probe, i = (i + 1) & tab.mask) {
-    uint64_t cur = __hip_atomic_load(&tab.key[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (cur == kEmpty) {
-      uint64_t expected = kEmpty;
-      if (__hip_atomic_compare_exchange_strong(&tab.key[i], &expected, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                               __HIP_MEMORY_SCOPE_AGENT)) {
-        *won = true;
-        return (int64_t)i;
-      }
-      cur = expected;
-    }
-    if (cur == key) return (int64_t)i;
-  }
-  return -1;
-}
-
 // start[offsets[s]] = 1 for every non-empty sentence s.
 __global__ void starts_kernel(const int64_t* offsets, int64_t n_sent, uint8_t* start) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -104,7 +76,7 @@ __global__ void starts_kernel(const int64_t* offsets, int64_t n_sent, uint8_t* s
   }
 }
 
-// Insert (idempotent): slot[i] of every eligible position.
+// Insert (idempotent): slot[i] of every eligible position. A pair's home slot is its key's splitmix64 hash.
 __global__ void insert_kernel(const int32_t* ids, const uint8_t* start, int64_t n, const ull* cnt, ull min_count,
                               Table tab, uint32_t* slot, ull* used, ull* fail) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -114,7 +86,8 @@ __global__ void insert_kernel(const int32_t* ids, const uint8_t* start, int64_t 
       const uint32_t a = (uint32_t)ids[i - 1], b = (uint32_t)ids[i];
       if (cnt[a] >= min_count && cnt[b] >= min_count) {
         bool won = false;
-        const int64_t j = claim(tab, (((uint64_t)a << 32) | b) + 1, &won);
+        const uint64_t key = (((uint64_t)a << 32) | b) + 1;
+        const int64_t j = claim<kMaxProbe>(tab.key, tab.mask, mix64(key) & tab.mask, key, &won);
         if (j < 0) {
           atomicAdd(fail, 1ull);
         } else {
@@ -134,48 +107,9 @@ __global__ void rehash_kernel(const uint64_t* from, int64_t from_cap, Table to, 
     const uint64_t k = from[i];
     if (k == kEmpty) continue;
     bool won = false;
-    const int64_t j = claim(to, k, &won);
+    const int64_t j = claim<kMaxProbe>(to.key, to.mask, mix64(k) & to.mask, k, &won);
     if (j < 0 || !won) atomicAdd(fail, 1ull);
   }
-}
-
-// count[key[t]] += 1 for every key[t] != kNone: per workgroup the adds go to
-// an LDS table first; a key that finds no LDS entry within 8 probes adds to
-// HBM directly. With kFirst, first[key[t]] is lowered to t as well.
-template <bool kFirst>
-__global__ __launch_bounds__(kBlock) void count_kernel(const uint32_t* key, int64_t n, ull* count, ull* first) {
-  __shared__ uint32_t lkey[kLdsSlots];
-  __shared__ uint32_t lcnt[kLdsSlots];
-  for (int h = threadIdx.x; h < kLdsSlots; h += kBlock) {
-    lkey[h] = kNone;
-    lcnt[h] = 0;
-  }
-  __syncthreads();
-  const int64_t per = (n + gridDim.x - 1) / gridDim.x;
-  const int64_t lo = (int64_t)blockIdx.x * per, hi = min(n, lo + per);
-  for (int64_t t = lo + threadIdx.x; t < hi; t += kBlock) {
-    const uint32_t s = key[t];
-    if (s == kNone) continue;
-    if (kFirst)
-      if ((ull)t < __hip_atomic_load(&first[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&first[s], (ull)t);
-    uint32_t h = (s * 2654435761u) >> 20;  // 12 bits
-    bool done = false;
-    for (int probe = 0; probe < 8 && !done; ++probe, h = (h + 1) & (kLdsSlots - 1)) {
-      uint32_t k = lkey[h];
-      if (k == kNone) {
-        const uint32_t old = atomicCAS(&lkey[h], kNone, s);
-        k = old == kNone ? s : old;  // claimed it, or another thread did
-      }
-      if (k == s) {
-        atomicAdd(&lcnt[h], 1u);
-        done = true;
-      }
-    }
-    if (!done) atomicAdd(&count[s], 1ull);
-  }
-  __syncthreads();
-  for (int h = threadIdx.x; h < kLdsSlots; h += kBlock)
-    if (lcnt[h]) atomicAdd(&count[lkey[h]], (ull)lcnt[h]);
 }
 
 // lastnc[i] = -1 where i is a candidate, else i (the max-scan's input).
@@ -217,18 +151,6 @@ struct Joined {
   const ull* firstjoin;
   __host__ __device__ bool operator()(const int64_t& i) const { return firstjoin[i] != kNever; }
 };
-struct Used {
-  const uint64_t* key;
-  __host__ __device__ bool operator()(const int64_t& i) const { return key[i] != kEmpty; }
-};
-struct NotNegative {
-  __host__ __device__ bool operator()(const int32_t& v) const { return v >= 0; }
-};
-
-__global__ void gather_ull_kernel(const int64_t* slots, int64_t m, const ull* src, ull* out) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < m; k += stride) out[k] = src[slots[k]];
-}
 
 // The joined pairs in order of first joined occurrence get ids base, base + 1, ...
 __global__ void assign_kernel(const int64_t* order, int64_t m, Table tab, int32_t base, int32_t* left, int32_t* right,
@@ -290,10 +212,6 @@ __global__ void map_kernel(const int32_t* ids, int64_t n, const int32_t* vidx, i
   }
 }
 
-inline dim3 grid_for(int64_t n) {
-  return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(8192, (n + kBlock - 1) / kBlock)));
-}
-
 }  // namespace phrase
 }  // namespace w2v
 
@@ -310,13 +228,22 @@ struct TableBuf {
   Table view() const {
     return Table{key.get(), count.get(), joined.get(), firstjoin.get(), pid.get(), (uint64_t)cap() - 1};
   }
+  // Becomes an empty table of `cap` slots (a power of two).
+  int alloc(int64_t cap, hipStream_t s) {
+    TableBuf t;
+    const size_t n = (size_t)cap;
+    int rc;
+    if ((rc = t.key.alloc(n)) || (rc = t.count.alloc(n)) || (rc = t.joined.alloc(n)) || (rc = t.firstjoin.alloc(n)) ||
+        (rc = t.pid.alloc(n)))
+      return rc;
+    W2V_HIP_TRY(hipMemsetAsync(t.key.get(), 0, n * sizeof(uint64_t), s));
+    W2V_HIP_TRY(hipMemsetAsync(t.count.get(), 0, n * sizeof(ull), s));
+    W2V_HIP_TRY(hipMemsetAsync(t.joined.get(), 0, n * sizeof(ull), s));
+    W2V_HIP_TRY(hipMemsetAsync(t.firstjoin.get(), 0xFF, n * sizeof(ull), s));
+    *this = std::move(t);
+    return W2V_OK;
+  }
 };
-
-int64_t pow2_at_least(int64_t v) {
-  int64_t c = 1;
-  while (c < v) c <<= 1;
-  return c;
-}
 
 }  // namespace
 
@@ -369,21 +296,6 @@ int ensure_init(w2v_phrase* p) {
   return W2V_OK;
 }
 
-int alloc_table(TableBuf& out, int64_t cap, hipStream_t s) {
-  TableBuf t;
-  const size_t n = (size_t)cap;
-  int rc;
-  if ((rc = t.key.alloc(n)) || (rc = t.count.alloc(n)) || (rc = t.joined.alloc(n)) || (rc = t.firstjoin.alloc(n)) ||
-      (rc = t.pid.alloc(n)))
-    return rc;
-  W2V_HIP_TRY(hipMemsetAsync(t.key.get(), 0, n * sizeof(uint64_t), s));
-  W2V_HIP_TRY(hipMemsetAsync(t.count.get(), 0, n * sizeof(ull), s));
-  W2V_HIP_TRY(hipMemsetAsync(t.joined.get(), 0, n * sizeof(ull), s));
-  W2V_HIP_TRY(hipMemsetAsync(t.firstjoin.get(), 0xFF, n * sizeof(ull), s));
-  out = std::move(t);
-  return W2V_OK;
-}
-
 // cnt[w] and first[w] of ids[0, n) over n_words ids.
 int histogram(w2v_phrase* p, const int32_t* ids, int64_t n, int64_t n_words, DevBuf<ull>& cnt, DevBuf<ull>& first) {
   const size_t m = (size_t)std::max<int64_t>(n_words, 1);
@@ -421,55 +333,6 @@ struct Clock {
     return s;
   }
 };
-
-// ExclusiveSum of flags[0, n) into pos and the total; temp is grown as needed.
-int exclusive_sum(w2v_phrase* p, const int32_t* flags, int32_t* pos, int64_t n, int64_t* total) {
-  size_t tb = 0;
-  W2V_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, flags, pos, (int)n, p->stream));
-  DevBuf<unsigned char> tmp;
-  if (int rc = tmp.alloc(std::max<size_t>(tb, 1))) return rc;
-  W2V_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp.get(), tb, flags, pos, (int)n, p->stream));
-  int32_t last_pos = 0, last_flag = 0;
-  W2V_HIP_TRY(hipMemcpyAsync(&last_pos, pos + n - 1, sizeof(int32_t), hipMemcpyDeviceToHost, p->stream));
-  W2V_HIP_TRY(hipMemcpyAsync(&last_flag, flags + n - 1, sizeof(int32_t), hipMemcpyDeviceToHost, p->stream));
-  W2V_HIP_TRY(hipStreamSynchronize(p->stream));
-  *total = (int64_t)last_pos + last_flag;
-  return W2V_OK;
-}
-
-// The slots of `tab` that satisfy `pred`, sorted ascending by sort_key[slot]
-// (gathered through `gather`): *m of them into order (and the sorted keys).
-template <class Pred, class Gather>
-int select_sorted(w2v_phrase* p, const TableBuf& tab, Pred pred, Gather gather, DevBuf<int64_t>& order,
-                  DevBuf<ull>& sorted_keys, int64_t* m_out) {
-  const int cap = (int)tab.cap();
-  DevBuf<int64_t> slots, n_sel;
-  DevBuf<ull> keys;
-  DevBuf<unsigned char> tmp;
-  int rc;
-  if ((rc = slots.alloc((size_t)cap)) || (rc = n_sel.alloc(1))) return rc;
-  hipcub::CountingInputIterator<int64_t> it(0);
-  size_t t1 = 0;
-  W2V_HIP_TRY(hipcub::DeviceSelect::If(nullptr, t1, it, slots.get(), n_sel.get(), cap, pred, p->stream));
-  if ((rc = tmp.alloc(std::max<size_t>(t1, 1)))) return rc;
-  W2V_HIP_TRY(hipcub::DeviceSelect::If(tmp.get(), t1, it, slots.get(), n_sel.get(), cap, pred, p->stream));
-  int64_t m = 0;
-  W2V_HIP_TRY(hipMemcpyAsync(&m, n_sel.get(), sizeof(int64_t), hipMemcpyDeviceToHost, p->stream));
-  W2V_HIP_TRY(hipStreamSynchronize(p->stream));
-  *m_out = m;
-  const size_t mm = (size_t)std::max<int64_t>(m, 1);
-  if ((rc = keys.alloc(mm)) || (rc = sorted_keys.alloc(mm)) || (rc = order.alloc(mm))) return rc;
-  if (m == 0) return W2V_OK;
-  if ((rc = gather(slots.get(), m, keys.get()))) return rc;
-  size_t t2 = 0;
-  W2V_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, t2, keys.get(), sorted_keys.get(), slots.get(), order.get(),
-                                                 (int)m, 0, 64, p->stream));
-  if ((rc = tmp.alloc(std::max<size_t>(t2, 1)))) return rc;
-  W2V_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.get(), t2, keys.get(), sorted_keys.get(), slots.get(), order.get(),
-                                                 (int)m, 0, 64, p->stream));
-  W2V_HIP_TRY(hipStreamSynchronize(p->stream));
-  return W2V_OK;
-}
 
 }  // namespace
 
@@ -564,7 +427,7 @@ int w2v_phrase_pass(w2v_phrase* p, int64_t min_count, float threshold) {
                                      : std::min<int64_t>(std::max<int64_t>(pow2_at_least(n), (int64_t)1 << 16),
                                                          (int64_t)1 << 26);
   TableBuf tab;
-  if ((rc = alloc_table(tab, cap, st))) return rc;
+  if ((rc = tab.alloc(cap, st))) return rc;
   double sec[5] = {0, 0, 0, 0, 0};
   if (n == 0) {
     p->tab = std::move(tab);
@@ -599,20 +462,13 @@ int w2v_phrase_pass(w2v_phrase* p, int64_t min_count, float threshold) {
     W2V_HIP_TRY(hipStreamSynchronize(st));
     used = c[0];
     if (c[1] == 0 && (int64_t)used * 2 <= tab.cap()) break;
-    int64_t bigger = tab.cap() * 2;
-    while (bigger < 2 * (int64_t)used) bigger <<= 1;
-    if (bigger > kMaxCap) return w2v::set_error(W2V_ERR_UNSUPPORTED, "w2v_phrase_pass: more than 2^29 distinct pairs");
-    TableBuf nt;
-    if ((rc = alloc_table(nt, bigger, st))) return rc;
-    W2V_HIP_TRY(hipMemsetAsync(ctr.get() + 1, 0, sizeof(ull), st));
-    hipLaunchKernelGGL(rehash_kernel, grid_for(tab.cap()), dim3(kBlock), 0, st, tab.key.get(), tab.cap(), nt.view(),
-                       ctr.get() + 1);
-    W2V_HIP_TRY(hipGetLastError());
-    ull f = 0;
-    W2V_HIP_TRY(hipMemcpyAsync(&f, ctr.get() + 1, sizeof(f), hipMemcpyDeviceToHost, st));
-    W2V_HIP_TRY(hipStreamSynchronize(st));
-    if (f) return w2v::set_error(W2V_ERR_STATE, "w2v_phrase_pass: rehash lost pairs");
-    tab = std::move(nt);
+    auto rehash = [&](const TableBuf& from, const TableBuf& to) {  // the keys alone: the counts are still zero
+      hipLaunchKernelGGL(rehash_kernel, grid_for(from.cap()), dim3(kBlock), 0, st, from.key.get(), from.cap(), to.view(),
+                         ctr.get() + 1);
+    };
+    if ((rc = grow(st, tab, (int64_t)used, ctr.get() + 1, rehash, "w2v_phrase_pass: more than 2^29 distinct pairs",
+                   "w2v_phrase_pass: rehash lost pairs")))
+      return rc;
   }
   sec[1] = clock.lap();
   hipLaunchKernelGGL(count_kernel<false>, grid_for(n / 16), dim3(kBlock), 0, st, slot.get(), n, tab.count.get(),
@@ -644,12 +500,7 @@ int w2v_phrase_pass(w2v_phrase* p, int64_t min_count, float threshold) {
   DevBuf<ull> sorted;
   int64_t P = 0;
   const Table tv = tab.view();
-  auto gather_firstjoin = [&](const int64_t* slots, int64_t m, ull* out) -> int {
-    hipLaunchKernelGGL(gather_ull_kernel, grid_for(m), dim3(kBlock), 0, st, slots, m, tv.firstjoin, out);
-    W2V_HIP_TRY(hipGetLastError());
-    return W2V_OK;
-  };
-  if ((rc = select_sorted(p, tab, Joined{tv.firstjoin}, gather_firstjoin, order, sorted, &P))) return rc;
+  if ((rc = select_sorted(st, tab.cap(), Joined{tv.firstjoin}, tv.firstjoin, order, sorted, &P))) return rc;
   if (p->n_words + P >= kMaxWords)
     return w2v::set_error(W2V_ERR_UNSUPPORTED, "w2v_phrase_pass: words + phrases must stay below 2^31");
   std::vector<int32_t> h_left((size_t)P), h_right((size_t)P);
@@ -667,7 +518,8 @@ int w2v_phrase_pass(w2v_phrase* p, int64_t min_count, float threshold) {
     W2V_HIP_TRY(hipStreamSynchronize(st));
   }
   int64_t n_out = 0;
-  if ((rc = exclusive_sum(p, keep.get(), outpos.get(), n, &n_out))) return rc;
+  DevBuf<unsigned char> scratch;
+  if ((rc = exclusive_sum(st, keep.get(), outpos.get(), n, &n_out, scratch))) return rc;
   DevBuf<int32_t> new_ids;
   DevBuf<int64_t> new_off;
   if ((rc = new_ids.alloc((size_t)std::max<int64_t>(n_out, 1))) || (rc = new_off.alloc((size_t)S + 1))) return rc;
@@ -737,13 +589,8 @@ int w2v_phrase_bigrams(w2v_phrase* p, int32_t* left, int32_t* right, int64_t* co
   DevBuf<ull> sorted;
   int64_t m = 0;
   int rc;
-  auto gather_key = [&](const int64_t* slots, int64_t k, ull* out) -> int {
-    hipLaunchKernelGGL(gather_ull_kernel, grid_for(k), dim3(kBlock), 0, st, slots, k,
-                       reinterpret_cast<const ull*>(tv.key), out);
-    W2V_HIP_TRY(hipGetLastError());
-    return W2V_OK;
-  };
-  if ((rc = select_sorted(p, p->tab, Used{tv.key}, gather_key, order, sorted, &m))) return rc;
+  if ((rc = select_sorted(st, p->tab.cap(), Used{tv.key}, reinterpret_cast<const ull*>(tv.key), order, sorted, &m)))
+    return rc;
   if (m != p->n_bigrams) return w2v::set_error(W2V_ERR_STATE, "w2v_phrase_bigrams: used-slot count mismatch");
   DevBuf<uint64_t> d_keys;
   DevBuf<int64_t> d_counts;
@@ -788,21 +635,15 @@ int w2v_phrase_map(w2v_phrase* p, const int32_t* vocab_index, int64_t n_words) {
   if (!p || (n_words > 0 && !vocab_index)) return w2v::set_error(W2V_ERR_ARG, "w2v_phrase_map: null argument");
   if (!p->loaded) return w2v::set_error(W2V_ERR_STATE, "w2v_phrase_map: upload or adopt a stream first");
   if (n_words != p->n_words) return w2v::set_error(W2V_ERR_ARG, "w2v_phrase_map: one vocab index per id of the stream");
-  int32_t vmax = -1;
-  for (int64_t k = 0; k < n_words; ++k) {
-    if (vocab_index[k] < -1) return w2v::set_error(W2V_ERR_ARG, "w2v_phrase_map: vocab_index entries must be >= -1");
-    vmax = std::max(vmax, vocab_index[k]);
-  }
   w2v::Range range_("w2v_phrase_map");
-  if (int rc = ensure_init(p)) return rc;
+  if (int rc = ensure_init(p)) return rc;  // the counts behind the vocab_index check are on the device
   hipStream_t st = p->stream;
   const int64_t n = p->n_ids, S = p->n_sentences;
   int rc;
-  // per-id token histogram: every occurrence of an in-vocab id is kept
-  std::vector<int64_t> cnt((size_t)n_words), hist((size_t)vmax + 1, 0);
+  std::vector<int64_t> cnt((size_t)n_words), hist;  // tokens per vocab id, from the stream's counts
   if (n_words > 0) W2V_HIP_TRY(hipMemcpy(cnt.data(), p->cnt.get(), n_words * sizeof(int64_t), hipMemcpyDeviceToHost));
-  for (int64_t k = 0; k < n_words; ++k)
-    if (vocab_index[k] >= 0) hist[(size_t)vocab_index[k]] += cnt[(size_t)k];
+  if (!vocab_hist(vocab_index, cnt.data(), n_words, hist))
+    return w2v::set_error(W2V_ERR_ARG, "w2v_phrase_map: vocab_index entries must be >= -1");
   DevBuf<int32_t> m_ids;
   DevBuf<int64_t> m_off;
   int64_t kept = 0;
@@ -818,7 +659,7 @@ int w2v_phrase_map(w2v_phrase* p, const int32_t* vocab_index, int64_t n_words) {
     hipLaunchKernelGGL(map_kernel, grid_for(n), dim3(kBlock), 0, st, p->ids.get(), n, d_vidx.get(), tok.get(),
                        flag.get());
     W2V_HIP_TRY(hipGetLastError());
-    if ((rc = exclusive_sum(p, flag.get(), kpos.get(), n, &kept))) return rc;
+    if ((rc = exclusive_sum(st, flag.get(), kpos.get(), n, &kept, tmp))) return rc;
     if ((rc = m_ids.alloc((size_t)std::max<int64_t>(kept, 1)))) return rc;
     size_t tb = 0;
     W2V_HIP_TRY(hipcub::DeviceSelect::If(nullptr, tb, tok.get(), m_ids.get(), n_sel.get(), (int)n, NotNegative(), st));
