@@ -280,6 +280,37 @@ class Word2Vec {
   // word, in vocabulary order (word2vec.c's format). Errors as most_similar's.
   std::vector<int32_t> word_classes(const RMatrixXf& data, int n_classes, int iterations = 10);
   void save_classes(const std::string& filename, const RMatrixXf& data, int n_classes, int iterations = 10);
+  // Sentence scores (gensim's score(); include/w2v_dev.h, w2v_dev_score): the
+  // log-likelihood of sentences under the host W / C / synapses1, every token a
+  // center with the full window, no subsampling; negative-sampling draws are
+  // Philox under score_key. score_ids takes token ids (indices of `vocab`,
+  // sentence s spans [offsets[s], offsets[s + 1])), score runs build_sample
+  // first (out-of-vocabulary tokens drop out as in training), score_file goes
+  // through file_samples. Each returns the sum over the sentences, fills the
+  // per-sentence sums / term counts when asked and leaves the whole summary in
+  // last_score. They upload the matrices as train does and change nothing
+  // else: not the matrices, the generator, current_words(), the checkpoint and
+  // resume state or the cached nearest-neighbour index; a train() after a
+  // score() gives what it would have given without it. Limits:
+  // w2v_dev_score_limits (window <= 127, negative <= 63). Bad arguments throw
+  // std::invalid_argument before any device call; device errors as most_similar's.
+  uint64_t score_key = 0;
+  w2v_score_summary last_score = w2v_score_summary();
+  double score_ids(const std::vector<int32_t>& ids, const std::vector<int64_t>& offsets,
+                   std::vector<double>* sentence_ll = nullptr, std::vector<int64_t>* sentence_targets = nullptr);
+  double score(std::vector<std::vector<std::string>>& sentences, std::vector<double>* sentence_ll = nullptr,
+               std::vector<int64_t>* sentence_targets = nullptr);
+  double score_file(const std::string& path, const std::string& format = "lines", int threads = 0,
+                    std::vector<double>* sentence_ll = nullptr, std::vector<int64_t>* sentence_targets = nullptr);
+  // Held-out objective per epoch: when heldout_ids is not empty, the
+  // single-device epoch loop scores it on the resident model after every epoch
+  // (no download) and appends the sum and the term count, next to
+  // epoch_seconds; the verbose line prints ll per target. With
+  // gpu_devices.size() >= 2 (replicas) both vectors stay empty.
+  std::vector<int32_t> heldout_ids;
+  std::vector<int64_t> heldout_offsets;
+  std::vector<double> epoch_heldout_ll;
+  std::vector<int64_t> epoch_heldout_targets;
   // Last device error (empty if none).
   std::string last_error;
 
@@ -315,6 +346,7 @@ class Word2Vec {
   void drop_phrases();
 
   bool uses_C() const;
+  void check_score_args(const std::vector<int32_t>& ids, const std::vector<int64_t>& offsets, const char* what) const;
   void check_limits() const;
   void finish_vocab(std::unordered_map<std::string, int>& tally);
   void ensure_device();

@@ -400,6 +400,55 @@ int w2v_dev_apply_rows(w2v_dev* h, float* rows, const uint8_t* codes, int32_t n,
                        float* grad, float alpha, int32_t hs_form);
 
 /* ---------------------------------------------------------------------------
+ * Sentence scores under the resident model (new: the reference has no loss;
+ * gensim's score()): the log-likelihood the training kernels ascend, read-only.
+ * Every token is a center with the full window (no subsampling, no window
+ * shrink). With logsig(z) = min(z, 0) - log1p(exp(-|z|)):
+ *   skip-gram HS  per (center i, context j), per node k of w_j's path:
+ *                 logsig((1 - 2 code_k) synapses1[point_k] . W[w_i])
+ *   CBOW HS       per center with N_i > 0 context positions, h_i = the sum of
+ *                 C over the distinct context ids (/ N_i with cbow_mean), per
+ *                 node k of w_i's path: logsig((1 - 2 code_k) synapses1[point_k] . h_i)
+ *   skip-gram NS  per (i, j): `negative` table draws with the training kernels'
+ *                 Philox counter (i, sentence, t << 8 | k, 0), t the ordinal of
+ *                 j among i's contexts, under the caller's key; logsig(C[w_j] .
+ *                 W[w_i]) and logsig(-C[u] . W[w_i]) for every distinct drawn
+ *                 u != w_j (the set semantics of Word2Vec.cpp:253-257)
+ *   CBOW NS       the same with input h_i, target matrix W, positive w_i, slot 0.
+ * out_ll[s] is the sum of sentence s's terms (a double), out_targets[s] their
+ * number; a sentence of <= 1 token has 0 / 0. The summary counts sentences,
+ * words (tokens), centers (with a context), contexts (skip-gram: pairs; CBOW:
+ * distinct ids), targets, draws and non-finite dot products, and ll is the sum
+ * of out_ll in sentence order. Dots and terms are fp32 in the kernels' lane
+ * layout; each lane adds its terms into an fp64 accumulator, one fixed-order
+ * sum per work item and a second pass in item order follow, with no float
+ * atomics: the same bits for every grid size, work-item size class and run.
+ * A non-finite dot product makes its sentence's ll NaN and is counted; the
+ * call still returns W2V_OK (a diverged model is reported, not refused).
+ *
+ * ids / sent_offsets are host arrays (ids in [0, vocab_size)), copied to
+ * buffers the handle keeps for the next call; both NULL scores the resident
+ * corpus (the out arrays then hold its sentence count). The resident corpus,
+ * order, progress counter, statistics, RNG mode and model are untouched; the
+ * shared-negatives update mode is ignored (the objective is the per-pair one).
+ * Synchronous: waits for the handle's stream first. out_ll, out_targets and
+ * summary may each be NULL. Limits (w2v_dev_score_limits): word_dim <= 2048,
+ * window <= 127, negative <= 63, and hs or negative, not both
+ * (W2V_ERR_UNSUPPORTED otherwise). A work item is up to `centers` consecutive
+ * centers of one sentence (w2v_dev_set_score_item: 0 = automatic, else a
+ * multiple of 64), so one long sentence still fills the device;
+ * w2v_dev_set_max_waves caps the scoring grid too.
+ * ------------------------------------------------------------------------- */
+typedef struct w2v_score_summary {
+  int64_t sentences, words, centers, contexts, targets, draws, nonfinite;
+  double ll;
+} w2v_score_summary;
+int w2v_dev_score_limits(int32_t* max_dim, int32_t* max_window, int32_t* max_negative); /* any pointer may be NULL */
+int w2v_dev_set_score_item(w2v_dev* h, int32_t centers);
+int w2v_dev_score(w2v_dev* h, const int32_t* ids, int64_t n_tokens, const int64_t* sent_offsets, int64_t n_sentences,
+                  uint64_t key, double* out_ll, int64_t* out_targets, w2v_score_summary* summary);
+
+/* ---------------------------------------------------------------------------
  * Multi-GPU data parallelism (BASELINE configs[3], configs[4] at 2/4/8 GPUs;
  * new: the reference has only OpenMP threads on one model, Word2Vec.cpp:375-394).
  * Every replica (a w2v_dev handle with its model resident; all replicas start

@@ -110,6 +110,27 @@ int w2v_model_analogy(w2v_model* m, const char* a, const char* b, const char* c,
  * one class id per row (-1 for a row with a non-finite element). */
 int w2v_model_word_classes(w2v_model* m, int32_t which, int32_t n_classes, int32_t iterations, int32_t* out);
 
+/* Word2Vec::score_ids / score / score_file (sentence log-likelihoods under the
+ * host matrices; include/w2v_dev.h w2v_dev_score) with Word2Vec::score_key =
+ * key. out_ll / out_targets (either may be NULL) take one entry per sentence:
+ * n_sent for score_ids; for the text (one sentence per line) and file forms
+ * the caller's arrays hold `cap` entries, *n_sent returns the count and a
+ * shorter array is an error. counts (NULL or 7 entries) returns the summary's
+ * sentences, words, centers, contexts, targets, draws, nonfinite; *sum its ll. */
+int w2v_model_score_ids(w2v_model* m, const int32_t* ids, const int64_t* offsets, int64_t n_sent, uint64_t key,
+                        double* out_ll, int64_t* out_targets, int64_t* counts, double* sum);
+int w2v_model_score(w2v_model* m, const char* text, int64_t len, uint64_t key, double* out_ll, int64_t* out_targets,
+                    int64_t cap, int64_t* n_sent, int64_t* counts, double* sum);
+int w2v_model_score_file(w2v_model* m, const char* path, const char* format, int32_t threads, uint64_t key,
+                         double* out_ll, int64_t* out_targets, int64_t cap, int64_t* n_sent, int64_t* counts,
+                         double* sum);
+/* Word2Vec::heldout_ids / heldout_offsets (+ score_key): scored after every
+ * epoch of a single-device train (n_sent = 0 or NULL turns it off);
+ * w2v_model_epoch_heldout returns epoch i's sum and term count of the last
+ * train call (non-zero when i is out of range). */
+int w2v_model_set_heldout(w2v_model* m, const int32_t* ids, const int64_t* offsets, int64_t n_sent, uint64_t key);
+int w2v_model_epoch_heldout(w2v_model* m, int64_t i, double* ll, int64_t* targets);
+
 int w2v_model_save(w2v_model* m, const char* path, int32_t which, int32_t binary);
 int w2v_model_load(w2v_model* m, const char* path, int32_t binary);
 int w2v_model_save_vocab(w2v_model* m, const char* path);

@@ -69,6 +69,16 @@ class DevStats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class ScoreSummary(C.Structure):
+    """Mirror of w2v_score_summary."""
+
+    _fields_ = [(k, C.c_int64) for k in ("sentences", "words", "centers", "contexts", "targets", "draws",
+                                          "nonfinite")] + [("ll", C.c_double)]
+
+    def as_dict(self):
+        return {k: (float if k == "ll" else int)(getattr(self, k)) for k, _ in self._fields_}
+
+
 class LaunchPlan(C.Structure):
     """Mirror of w2v_launch_plan."""
 
@@ -145,6 +155,10 @@ SIGNATURES = {
     "w2v_dev_set_max_waves": (C.c_int, [_P, _I64]),
     "w2v_dev_set_update": (C.c_int, [_P, _I32]),
     "w2v_dev_apply_rows": (C.c_int, [_P, _P, _P, _I32, _P, _P, _F, _I32]),
+    # sentence scores under the resident model
+    "w2v_dev_score_limits": (C.c_int, [C.POINTER(_I32)] * 3),
+    "w2v_dev_set_score_item": (C.c_int, [_P, _I32]),
+    "w2v_dev_score": (C.c_int, [_P, _P, _I64, _P, _I64, _U64, _P, _P, C.POINTER(ScoreSummary)]),
     "w2v_group_unique_id": (C.c_int, [_P]),
     "w2v_group_create": (C.c_int, [_P, _I32, _P, _I32, _I32, C.POINTER(_P)]),
     "w2v_group_destroy": (None, [_P]),

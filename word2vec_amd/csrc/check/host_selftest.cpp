@@ -163,6 +163,46 @@ int main(int argc, char** argv) {
     }
     expect(threw && w.last_error.find("no-such-word") != std::string::npos, "Word2Vec::analogy unknown word");
   }
+  {  // score_ids: the host-side argument checks come before any device call
+    Word2Vec w(1, 5, 2, 20000, 16, 5, 1e-3f, 0.025f, 1e-6f, true, 1, "ns", "sg");
+    w.build_vocab(sents);
+    w.init_weights(w.vocab.size());
+    auto refused = [&](const std::vector<int32_t>& ids, const std::vector<int64_t>& off) {
+      try {
+        w.score_ids(ids, off);
+      } catch (const std::invalid_argument&) {
+        return true;
+      } catch (...) {
+      }
+      return false;
+    };
+    const int32_t V = (int32_t)w.vocab.size();
+    expect(refused({0, 1}, {}), "score_ids: empty offsets");
+    expect(refused({0, 1}, {0, 1}), "score_ids: offsets short of the ids");
+    expect(refused({0, 1}, {1, 2}), "score_ids: offsets not from 0");
+    expect(refused({0, 1, 0}, {0, 2, 1, 3}), "score_ids: decreasing offsets");
+    expect(refused({0, V}, {0, 2}), "score_ids: id past the vocabulary");
+    expect(refused({-1, 0}, {0, 2}), "score_ids: negative id");
+    w.window = 128;
+    expect(refused({0, 1}, {0, 2}), "score_ids: window past the scoring limit");
+    w.window = 5;
+    w.negative = 64;
+    expect(refused({0, 1}, {0, 2}), "score_ids: negative past the scoring limit");
+    w.negative = 5;
+    w.W.resize(1, 16);
+    expect(refused({0, 1}, {0, 2}), "score_ids: matrices of another shape");
+    w.heldout_ids = {0, V};
+    w.heldout_offsets = {0, 2};
+    std::vector<int32_t> ids{0, 1};
+    std::vector<int64_t> off{0, 2};
+    bool threw = false;
+    try {
+      w.train_ids(ids, off, 2);
+    } catch (const std::invalid_argument&) {
+      threw = true;
+    }
+    expect(threw, "train: a bad held-out set is refused before any device call");
+  }
   std::printf("host selftest: %d failure(s)\n", failures);
   return failures ? 1 : 0;
 }

@@ -19,6 +19,7 @@
 #include "w2v_kernels.hpp"
 #include "w2v_launch.hpp"
 #include "w2v_policy.hpp"
+#include "w2v_score.hpp"
 #include "w2v_shared.hpp"
 
 namespace w2v {
@@ -147,6 +148,13 @@ struct w2v_dev {
   // the device copy of last_plan.hot_sc and the scales it holds
   std::vector<float> hot_sc_h;
   w2v::DevBuf<float> hot_sc_d;
+  // w2v_dev_score: the scored arrays, their work items and the partials (reused across calls)
+  int32_t score_item = 0;  // centers per work item (0: automatic)
+  w2v::DevBuf<int32_t> score_ids;
+  w2v::DevBuf<int64_t> score_soff, score_item_off, score_part_targets, score_targets;
+  w2v::DevBuf<double> score_part_ll, score_ll;
+  w2v::DevBuf<uint32_t> score_part_nonfinite;
+  w2v::DevBuf<unsigned long long> score_ctr;
 
   ~w2v_dev() {  // the buffers free themselves after this
     (void)hipSetDevice(device);
@@ -269,6 +277,13 @@ int init_device(w2v_dev* h) {
   W2V_HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->device));
   h->n_cu = ncu > 0 ? ncu : 256;
   return W2V_OK;
+}
+
+// At least n elements (the contents are not kept).
+template <class T>
+int score_grow(w2v::DevBuf<T>& b, int64_t n) {
+  const size_t need = (size_t)(n > 0 ? n : 1);
+  return b.size() >= need ? W2V_OK : b.alloc(need);
 }
 
 }  // namespace
@@ -1252,6 +1267,129 @@ int w2v_dev_apply_rows(w2v_dev* h, float* rows, const uint8_t* codes, int32_t n,
   if (n > 0)
     W2V_HIP_TRY(hipMemcpy2DAsync(rows, d * sizeof(float), dr, dp, d * sizeof(float), n, hipMemcpyDeviceToHost, h->stream));
   W2V_HIP_TRY(hipStreamSynchronize(h->stream));
+  return W2V_OK;
+}
+
+int w2v_dev_score_limits(int32_t* max_dim, int32_t* max_window, int32_t* max_negative) {
+  if (max_dim) *max_dim = w2v::kScoreMaxDim;
+  if (max_window) *max_window = w2v::kScoreMaxWindow;
+  if (max_negative) *max_negative = w2v::kScoreMaxNegative;
+  return W2V_OK;
+}
+
+int w2v_dev_set_score_item(w2v_dev* h, int32_t centers) {
+  if (centers < 0 || centers % w2v::kWave != 0)
+    return fail(W2V_ERR_ARG, "w2v_dev_set_score_item: centers must be 0 (automatic) or a multiple of 64");
+  if (!h) return fail(W2V_ERR_ARG, "w2v_dev_set_score_item: null handle");
+  h->score_item = centers;
+  return W2V_OK;
+}
+
+int w2v_dev_score(w2v_dev* h, const int32_t* ids, int64_t n_tok, const int64_t* soff, int64_t n_sent, uint64_t key,
+                  double* out_ll, int64_t* out_targets, w2v_score_summary* summary) {
+  w2v::Range range_("w2v_dev_score");
+  if (!h) return fail(W2V_ERR_ARG, "w2v_dev_score: null handle");
+  const w2v_dev_config& cfg = h->cfg;
+  if (cfg.word_dim > w2v::kScoreMaxDim)
+    return fail(W2V_ERR_UNSUPPORTED, "w2v_dev_score: word_dim > " + std::to_string(w2v::kScoreMaxDim) + " unsupported");
+  if (cfg.window > w2v::kScoreMaxWindow)
+    return fail(W2V_ERR_UNSUPPORTED, "w2v_dev_score: window > " + std::to_string(w2v::kScoreMaxWindow) +
+                                         " unsupported (a window's distinct ids are held in registers)");
+  if (cfg.negative > w2v::kScoreMaxNegative)
+    return fail(W2V_ERR_UNSUPPORTED, "w2v_dev_score: negative > " + std::to_string(w2v::kScoreMaxNegative) +
+                                         " unsupported (a context's draws are one wave pass)");
+  if (cfg.hs && cfg.negative > 0)
+    return fail(W2V_ERR_UNSUPPORTED, "w2v_dev_score: hs together with negative > 0 has no single objective");
+  if (!h->vocab_ready) return fail(W2V_ERR_STATE, "w2v_dev_score: upload the vocab first");
+  if (!h->model_ready) return fail(W2V_ERR_STATE, "w2v_dev_score: upload the model first");
+  if (!cfg.hs && !h->table.get()) return fail(W2V_ERR_STATE, "w2v_dev_score: no unigram table on the device");
+  const bool resident = !ids && !soff;
+  if (resident) {
+    if (!h->corpus_ready) return fail(W2V_ERR_STATE, "w2v_dev_score: no resident corpus to score (ids == NULL)");
+    n_tok = h->n_tok;
+    n_sent = h->n_sent;
+  } else {
+    if (!soff || (n_tok > 0 && !ids)) return fail(W2V_ERR_ARG, "w2v_dev_score: null argument");
+    if (n_sent < 0 || n_tok < 0 || n_sent > (int64_t)UINT32_MAX - 1)
+      return fail(W2V_ERR_ARG, "w2v_dev_score: sizes out of range");
+    if (soff[0] != 0 || soff[n_sent] != n_tok)
+      return fail(W2V_ERR_ARG, "w2v_dev_score: sentence offsets must span [0, n_tokens]");
+    for (int64_t s = 0; s < n_sent; ++s)
+      if (soff[s] > soff[s + 1] || soff[s + 1] - soff[s] > (int64_t)INT32_MAX)
+        return fail(W2V_ERR_ARG, "w2v_dev_score: sentence offsets must be non-decreasing");
+    for (int64_t t = 0; t < n_tok; ++t)
+      if (ids[t] < 0 || ids[t] >= h->V) return fail(W2V_ERR_ARG, "w2v_dev_score: token id out of vocab range");
+  }
+  if (set_device(h)) return W2V_ERR_HIP;
+  W2V_HIP_TRY(hipStreamSynchronize(h->stream));  // the training enqueued so far has written the model
+  // the work items: up to `item` consecutive centers of one sentence
+  std::vector<int64_t> off_h;
+  if (resident) {
+    off_h.resize((size_t)n_sent + 1);
+    W2V_HIP_TRY(hipMemcpy(off_h.data(), h->corpus->soff.get(), off_h.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+    soff = off_h.data();
+  }
+  const int64_t item = h->score_item > 0 ? h->score_item : w2v::kScoreAutoItem;
+  std::vector<int64_t> item_off((size_t)n_sent + 1, 0);
+  for (int64_t s = 0; s < n_sent; ++s) item_off[(size_t)s + 1] = item_off[(size_t)s] + (soff[s + 1] - soff[s] + item - 1) / item;
+  const int64_t n_items = item_off[(size_t)n_sent];
+  int rc;
+  if ((rc = score_grow(h->score_item_off, n_sent + 1)) || (rc = score_grow(h->score_part_ll, n_items)) ||
+      (rc = score_grow(h->score_part_targets, n_items)) || (rc = score_grow(h->score_part_nonfinite, n_items)) ||
+      (rc = score_grow(h->score_ll, n_sent)) || (rc = score_grow(h->score_targets, n_sent)) ||
+      (rc = score_grow(h->score_ctr, w2v::kScoreCounters)))
+    return rc;
+  if (!resident) {
+    if ((rc = score_grow(h->score_ids, n_tok)) || (rc = score_grow(h->score_soff, n_sent + 1))) return rc;
+    if (n_tok > 0) W2V_HIP_TRY(hipMemcpy(h->score_ids.get(), ids, n_tok * sizeof(int32_t), hipMemcpyHostToDevice));
+    W2V_HIP_TRY(hipMemcpy(h->score_soff.get(), soff, (n_sent + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+  }
+  W2V_HIP_TRY(hipMemcpy(h->score_item_off.get(), item_off.data(), item_off.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+  w2v::ScoreArgs a{};
+  a.W = h->W; a.C = h->C; a.S = h->S; a.pitch = h->pitch;
+  a.window = cfg.window; a.negative = cfg.negative; a.cbow_mean = cfg.cbow_mean; a.item = (int32_t)item;
+  a.ids = resident ? h->corpus->ids.get() : h->score_ids.get();
+  a.soff = resident ? h->corpus->soff.get() : h->score_soff.get();
+  a.item_off = h->score_item_off.get(); a.n_sent = n_sent; a.n_items = n_items;
+  a.table = h->table.get(); a.table_size = cfg.table_size;
+  a.codes = h->codes.get(); a.points = h->points.get(); a.coff = h->coff.get();
+  a.key0 = (uint32_t)key; a.key1 = (uint32_t)(key >> 32);
+  a.part_ll = h->score_part_ll.get(); a.part_targets = h->score_part_targets.get();
+  a.part_nonfinite = h->score_part_nonfinite.get(); a.ctr = h->score_ctr.get();
+  a.ll = h->score_ll.get(); a.targets = h->score_targets.get();
+  if ((rc = w2v::score_launch(a, h->nv, cfg.cbow != 0, cfg.hs != 0, h->set.max_waves, h->n_cu, h->stream))) return rc;
+  W2V_HIP_TRY(hipStreamSynchronize(h->stream));
+  std::vector<double> ll_h;
+  if (!out_ll && summary) {  // the summary's ll is the sentences' sum, in sentence order
+    ll_h.resize((size_t)n_sent);
+    out_ll = ll_h.data();
+  }
+  if (out_ll && n_sent > 0) W2V_HIP_TRY(hipMemcpy(out_ll, a.ll, n_sent * sizeof(double), hipMemcpyDeviceToHost));
+  if (out_targets && n_sent > 0)
+    W2V_HIP_TRY(hipMemcpy(out_targets, a.targets, n_sent * sizeof(int64_t), hipMemcpyDeviceToHost));
+  if (summary) {
+    unsigned long long c[w2v::kScoreCounters];
+    W2V_HIP_TRY(hipMemcpy(c, a.ctr, sizeof(c), hipMemcpyDeviceToHost));
+    std::vector<int64_t> tg_h;
+    const int64_t* tg = out_targets;
+    if (!tg && n_sent > 0) {
+      tg_h.resize((size_t)n_sent);
+      W2V_HIP_TRY(hipMemcpy(tg_h.data(), a.targets, n_sent * sizeof(int64_t), hipMemcpyDeviceToHost));
+      tg = tg_h.data();
+    }
+    w2v_score_summary r{};
+    r.sentences = n_sent;
+    r.words = n_tok;
+    r.centers = (int64_t)c[w2v::kScoreCenters];
+    r.contexts = (int64_t)c[w2v::kScoreContexts];
+    r.draws = (int64_t)c[w2v::kScoreDraws];
+    r.nonfinite = (int64_t)c[w2v::kScoreNonFinite];
+    for (int64_t s = 0; s < n_sent; ++s) {
+      r.targets += tg[s];
+      r.ll += out_ll[s];
+    }
+    *summary = r;
+  }
   return W2V_OK;
 }
 

@@ -494,10 +494,13 @@ void Word2Vec::append_reference_draws(const std::vector<int32_t>& ids, const std
 // The epoch loop of Word2Vec.cpp:367-395 with the model resident in HBM.
 void Word2Vec::run_epochs(const std::vector<int32_t>& ids, const std::vector<int64_t>& offsets,
                           int64_t train_words) {
+  epoch_heldout_ll.clear();  // stay empty with replicas (Word2Vec.h)
+  epoch_heldout_targets.clear();
   if (gpu_devices.size() > 1) {
     run_epochs_replicas(ids, offsets, train_words);
     return;
   }
+  if (!heldout_ids.empty()) check_score_args(heldout_ids, heldout_offsets, "heldout");
   ensure_device();
   upload_vocab_products();
   check(w2v_dev_upload_model(dev_, W.data(), uses_C() ? C.data() : nullptr,
@@ -564,8 +567,17 @@ void Word2Vec::run_epochs(const std::vector<int32_t>& ids, const std::vector<int
             "w2v_dev_download_model");
       checkpoint_epoch(cw, it + 1, key);
     }
+    w2v_score_summary held = w2v_score_summary();
+    if (!heldout_ids.empty()) {  // the held-out objective of the resident model (read-only; no download)
+      check(w2v_dev_score(dev_, heldout_ids.data(), (int64_t)heldout_ids.size(), heldout_offsets.data(),
+                          (int64_t)heldout_offsets.size() - 1, score_key, nullptr, nullptr, &held),
+            "w2v_dev_score");
+      epoch_heldout_ll.push_back(held.ll);
+      epoch_heldout_targets.push_back(held.targets);
+    }
     if (verbose) {
       std::printf("\rinit_alpha: %f  Progress: %f%% ", init_alpha, 100.0 / iter * cw / train_words);
+      if (held.targets > 0) std::printf(" held-out ll per target: %f ", held.ll / (double)held.targets);
       std::fflush(stdout);
     }
   }
@@ -800,6 +812,73 @@ void Word2Vec::train_ids(const std::vector<int32_t>& ids, const std::vector<int6
   drop_index();
   if (!resume_) init_weights(vocab.size());
   run_epochs(ids, offsets, train_words);
+}
+
+// ---------------------------------------------------------------------------
+// Sentence scores (additive; include/w2v_dev.h, w2v_dev_score).
+// ---------------------------------------------------------------------------
+// What the host can check without a device: the arrays' shape, the ids' range
+// and that the matrices the objective reads match the vocabulary.
+void Word2Vec::check_score_args(const std::vector<int32_t>& ids, const std::vector<int64_t>& offsets,
+                                const char* what) const {
+  auto bad = [&](const std::string& why) { throw std::invalid_argument(std::string("word2vec_amd: ") + what + ": " + why); };
+  if (offsets.empty() || offsets.front() != 0 || offsets.back() != (int64_t)ids.size())
+    bad("offsets must hold n_sentences + 1 entries spanning [0, ids.size()]");
+  for (size_t s = 0; s + 1 < offsets.size(); ++s)
+    if (offsets[s] > offsets[s + 1]) bad("offsets must be non-decreasing");
+  const int64_t V = (int64_t)vocab.size();
+  for (int32_t id : ids)
+    if (id < 0 || id >= V) bad("token id " + std::to_string(id) + " outside the vocabulary");
+  int32_t md = 0, mw = 0, mn = 0;
+  (void)w2v_dev_score_limits(&md, &mw, &mn);
+  if (word_dim < 1 || word_dim > md) bad("word_dim must be in [1, " + std::to_string(md) + "]");
+  if (window < 0 || window > mw) bad("window must be in [0, " + std::to_string(mw) + "] to score");
+  if (negative < 0 || negative > mn) bad("negative must be in [0, " + std::to_string(mn) + "] to score");
+}
+
+double Word2Vec::score_ids(const std::vector<int32_t>& ids, const std::vector<int64_t>& offsets,
+                           std::vector<double>* sentence_ll, std::vector<int64_t>* sentence_targets) {
+  check_score_args(ids, offsets, "score_ids");
+  const bool hs = train_method == "hs";
+  const int64_t V = (int64_t)vocab.size();
+  auto shaped = [&](const RMatrixXf& M, int64_t rows) { return (int64_t)M.rows() == rows && (int64_t)M.cols() == word_dim; };
+  if (V < 1 || !shaped(W, V) || (uses_C() && !shaped(C, V)) || (hs && !shaped(synapses1, V - 1)))
+    throw std::invalid_argument("word2vec_amd: score_ids: no trained model of this vocabulary's shape (W, C, synapses1)");
+  ensure_device();
+  upload_vocab_products();
+  check(w2v_dev_upload_model(dev_, W.data(), uses_C() ? C.data() : nullptr, hs ? synapses1.data() : nullptr),
+        "w2v_dev_upload_model");
+  check(w2v_dev_set_max_waves(dev_, max_waves), "w2v_dev_set_max_waves");
+  const int64_t n = (int64_t)offsets.size() - 1;
+  if (sentence_ll) sentence_ll->assign((size_t)n, 0.0);
+  if (sentence_targets) sentence_targets->assign((size_t)n, 0);
+  w2v_score_summary sm = w2v_score_summary();
+  check(w2v_dev_score(dev_, ids.data(), (int64_t)ids.size(), offsets.data(), n, score_key,
+                      sentence_ll ? sentence_ll->data() : nullptr, sentence_targets ? sentence_targets->data() : nullptr,
+                      &sm),
+        "w2v_dev_score");
+  last_score = sm;
+  return sm.ll;
+}
+
+double Word2Vec::score(std::vector<std::vector<std::string>>& sentences, std::vector<double>* sentence_ll,
+                       std::vector<int64_t>* sentence_targets) {
+  std::vector<int32_t> ids;
+  std::vector<int64_t> offsets(1, 0);
+  for (auto& kept : build_sample(sentences)) {
+    for (const Word* w : kept) ids.push_back((int32_t)w->index);
+    offsets.push_back((int64_t)ids.size());
+  }
+  return score_ids(ids, offsets, sentence_ll, sentence_targets);
+}
+
+double Word2Vec::score_file(const std::string& path, const std::string& format, int threads,
+                            std::vector<double>* sentence_ll, std::vector<int64_t>* sentence_targets) {
+  std::vector<int32_t> ids;
+  std::vector<int64_t> offsets;
+  int64_t raw = 0;
+  file_samples(path, format, threads, ids, offsets, raw);
+  return score_ids(ids, offsets, sentence_ll, sentence_targets);
 }
 
 // ---------------------------------------------------------------------------

@@ -8,8 +8,9 @@
 // is written (:196-201). Additive: -train is honoured (the reference always
 // reads ./text8), -binary, -gpu, -replay, -shared-negatives, and the
 // multi-GPU flags -gpus, -sync-words, -overlap, -replica-mode (Word2Vec::gpu_devices), -gpu-ingest,
-// -classes (in the reference's help text, never parsed by its main), and
-// -phrase / -phrase-min-count (word2phrase passes before the vocabulary).
+// -classes (in the reference's help text, never parsed by its main),
+// -phrase / -phrase-min-count (word2phrase passes before the vocabulary), and
+// -score / -score-output (the trained model's log-likelihood of a text).
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -54,7 +55,10 @@ void usage() {
                "                        GPU, one \"word class\" line per word (default 0: vectors are written)\n"
                "  -phrase <t1[,t2...]>  join word pairs into phrases (new_york) on the GPU before training: one word2phrase\n"
                "                        pass per comma-separated threshold >= 0, e.g. 200,100 (default: off)\n"
-               "  -phrase-min-count <int> words and pairs rarer than this never join (default 5)\n\n"
+               "  -phrase-min-count <int> words and pairs rarer than this never join (default 5)\n"
+               "  -score <file>         after training, score this text (read as -train is) under the model on the GPU and\n"
+               "                        print its sentences, targets, log-likelihood and log-likelihood per target\n"
+               "  -score-output <file>  with -score: one \"log-likelihood targets\" line per sentence\n\n"
                "example: ./word2vec -train text8 -output vec.txt -size 300 -window 5 -subsample 1e-4 "
                "-negative 5 -model sg -train_method ns -iter 3\n";
 }
@@ -112,6 +116,13 @@ int main(int argc, char** argv) {
   if ((i = find_flag("-replica-mode", argc, argv)) > 0) replica_mode = argv[i + 1];
   if ((i = find_flag("-gpu-ingest", argc, argv)) > 0) gpu_ingest = std::atoi(argv[i + 1]);
   if ((i = find_flag("-classes", argc, argv)) > 0) classes = std::atoi(argv[i + 1]);
+  std::string score_file = "", score_output = "";
+  if ((i = find_flag("-score", argc, argv)) > 0) score_file = argv[i + 1];
+  if ((i = find_flag("-score-output", argc, argv)) > 0) score_output = argv[i + 1];
+  if (score_file.empty() && !score_output.empty()) {
+    std::cout << "Please set -score with -score-output!" << std::endl;
+    return 1;
+  }
   std::vector<float> phrase_thresholds;
   int phrase_min_count = 5;
   bool phrase_ok = true;
@@ -187,6 +198,12 @@ int main(int argc, char** argv) {
       std::cout << "Please set -negative <= " << mn << " (the GPU kernels' range)!" << std::endl;
       return 1;
     }
+    int32_t cw = 0, cn = 0;
+    w2v_dev_score_limits(nullptr, &cw, &cn);
+    if (!score_file.empty() && (window > cw || negative > cn)) {
+      std::cout << "Please set -window <= " << cw << " and -negative <= " << cn << " with -score!" << std::endl;
+      return 1;
+    }
     int32_t sdim = 0;
     w2v_dev_shared_limits(&sdim, nullptr, nullptr);
     if (shared && (window > smw || negative > smn || word_dim > sdim)) {
@@ -242,6 +259,25 @@ int main(int argc, char** argv) {
       }
     } else {
       w2v.save_word2vec(output_file, out, binary != 0);
+    }
+  }
+  if (!score_file.empty()) {
+    try {
+      std::vector<double> ll;
+      std::vector<int64_t> targets;
+      const double total = w2v.score_file(score_file, "text8", 0, &ll, &targets);
+      const w2v_score_summary& sm = w2v.last_score;
+      std::printf("score: sentences %lld targets %lld ll %.17g ll_per_target %.17g\n", (long long)sm.sentences,
+                  (long long)sm.targets, total, sm.targets > 0 ? total / (double)sm.targets : 0.0);
+      if (!score_output.empty()) {
+        std::FILE* f = std::fopen(score_output.c_str(), "w");
+        if (!f) throw std::runtime_error("cannot write " + score_output);
+        for (size_t s = 0; s < ll.size(); ++s) std::fprintf(f, "%.17g %lld\n", ll[s], (long long)targets[s]);
+        std::fclose(f);
+      }
+    } catch (const std::exception& e) {
+      std::cerr << e.what() << std::endl;
+      return 2;
     }
   }
   return 0;

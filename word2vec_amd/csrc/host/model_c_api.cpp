@@ -362,4 +362,80 @@ int w2v_model_precalc_sampling(w2v_model* m) {
   return guard(m, [&] { m->w.precalc_sampling(); });
 }
 
+// Word2Vec::score_ids / score / score_file: the per-sentence arrays come back
+// through a vector pair, the summary as 7 counts and the sum.
+namespace {
+void copy_scores(const Word2Vec& w, const std::vector<double>& ll, const std::vector<int64_t>& tg, double* out_ll,
+                 int64_t* out_targets, int64_t cap, int64_t* n_sent, int64_t* counts, double* sum) {
+  const int64_t n = (int64_t)ll.size();
+  if (n_sent) *n_sent = n;
+  if ((out_ll || out_targets) && cap < n) throw std::invalid_argument("score: the output arrays are shorter than the sentences");
+  if (out_ll && n > 0) std::memcpy(out_ll, ll.data(), (size_t)n * sizeof(double));
+  if (out_targets && n > 0) std::memcpy(out_targets, tg.data(), (size_t)n * sizeof(int64_t));
+  const w2v_score_summary& s = w.last_score;
+  const int64_t c[7] = {s.sentences, s.words, s.centers, s.contexts, s.targets, s.draws, s.nonfinite};
+  if (counts) std::memcpy(counts, c, sizeof(c));
+  if (sum) *sum = s.ll;
+}
+}  // namespace
+
+int w2v_model_score_ids(w2v_model* m, const int32_t* ids, const int64_t* offsets, int64_t n_sent, uint64_t key,
+                        double* out_ll, int64_t* out_targets, int64_t* counts, double* sum) {
+  return guard(m, [&] {
+    if (!offsets || n_sent < 0 || offsets[n_sent] < 0 || (offsets[n_sent] > 0 && !ids))
+      throw std::invalid_argument("score_ids: null or negative argument");
+    std::vector<int32_t> i(ids, ids + offsets[n_sent]);
+    std::vector<int64_t> o(offsets, offsets + n_sent + 1);
+    std::vector<double> ll;
+    std::vector<int64_t> tg;
+    m->w.score_key = key;
+    m->w.score_ids(i, o, &ll, &tg);
+    copy_scores(m->w, ll, tg, out_ll, out_targets, n_sent, nullptr, counts, sum);
+  });
+}
+
+int w2v_model_score(w2v_model* m, const char* text, int64_t len, uint64_t key, double* out_ll, int64_t* out_targets,
+                    int64_t cap, int64_t* n_sent, int64_t* counts, double* sum) {
+  return guard(m, [&] {
+    auto s = parse(text, len);
+    std::vector<double> ll;
+    std::vector<int64_t> tg;
+    m->w.score_key = key;
+    m->w.score(s, &ll, &tg);
+    copy_scores(m->w, ll, tg, out_ll, out_targets, cap, n_sent, counts, sum);
+  });
+}
+
+int w2v_model_score_file(w2v_model* m, const char* path, const char* format, int32_t threads, uint64_t key,
+                         double* out_ll, int64_t* out_targets, int64_t cap, int64_t* n_sent, int64_t* counts,
+                         double* sum) {
+  return guard(m, [&] {
+    std::vector<double> ll;
+    std::vector<int64_t> tg;
+    m->w.score_key = key;
+    m->w.score_file(path, format, threads, &ll, &tg);
+    copy_scores(m->w, ll, tg, out_ll, out_targets, cap, n_sent, counts, sum);
+  });
+}
+
+int w2v_model_set_heldout(w2v_model* m, const int32_t* ids, const int64_t* offsets, int64_t n_sent, uint64_t key) {
+  return guard(m, [&] {
+    m->w.score_key = key;
+    if (!ids || !offsets || n_sent <= 0 || offsets[n_sent] <= 0) {  // off
+      m->w.heldout_ids.clear();
+      m->w.heldout_offsets.clear();
+      return;
+    }
+    m->w.heldout_ids.assign(ids, ids + offsets[n_sent]);
+    m->w.heldout_offsets.assign(offsets, offsets + n_sent + 1);
+  });
+}
+
+int w2v_model_epoch_heldout(w2v_model* m, int64_t i, double* ll, int64_t* targets) {
+  if (i < 0 || i >= (int64_t)m->w.epoch_heldout_ll.size()) return 1;
+  if (ll) *ll = m->w.epoch_heldout_ll[(size_t)i];
+  if (targets) *targets = m->w.epoch_heldout_targets[(size_t)i];
+  return 0;
+}
+
 }  // extern "C"

@@ -302,6 +302,32 @@ class DeviceTrainer:
         """Cap on wavefronts in flight (0 = as many as fit)."""
         self._chk(self.lib.w2v_dev_set_max_waves(self.h, int(n)), "w2v_dev_set_max_waves")
 
+    def score(self, ids=None, offsets=None, key: int = 0, item: int = 0) -> dict:
+        """w2v_dev_score: the log-likelihood of each sentence under the resident model (every token a center,
+        full window; include/w2v_dev.h). ids / offsets None = the resident corpus. `item` = centers per work
+        item (0 automatic, else a multiple of 64). Returns ll (float64 per sentence), targets (int64 per
+        sentence), the summary's counts and its ll under their own names, and per_target = ll / targets."""
+        self._chk(self.lib.w2v_dev_set_score_item(self.h, int(item)), "w2v_dev_set_score_item")
+        if ids is None:
+            if offsets is not None:
+                raise ValueError("score: offsets without ids")
+            i = o = None
+            n_tok, n_sent = 0, getattr(self, "n_sent", 0)
+        else:
+            i = np.ascontiguousarray(ids, dtype=np.int32)
+            o = np.ascontiguousarray(offsets, dtype=np.int64)
+            if o.size < 1:
+                raise ValueError("score: offsets must hold n_sentences + 1 entries")
+            n_tok, n_sent = i.size, o.size - 1
+        ll = np.zeros(n_sent, np.float64)
+        tg = np.zeros(n_sent, np.int64)
+        sm = N.ScoreSummary()
+        self._chk(self.lib.w2v_dev_score(self.h, _ptr(i), n_tok, _ptr(o), n_sent, int(key) & ((1 << 64) - 1),
+                                         _ptr(ll), _ptr(tg), C.byref(sm)), "w2v_dev_score")
+        out = {"ll": ll, "targets": tg, "summary": sm.as_dict()}
+        out["per_target"] = sm.ll / sm.targets if sm.targets else 0.0
+        return out
+
     def set_update(self, mode: int):
         """W2V_UPDATE_PER_PAIR (the reference's, default) or W2V_UPDATE_SHARED_NEGATIVES
         (minibatch skip-gram on the matrix cores, BASELINE configs[4]); include/w2v_dev.h."""

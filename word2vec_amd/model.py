@@ -79,6 +79,13 @@ def _load():
             "w2v_model_replica_rounds": (I64, [P]),
             "w2v_model_replica_max_diff": (C.c_double, [P]),
             "w2v_model_read_vocab": (C.c_int, [P, S]),
+            "w2v_model_score_ids": (C.c_int, [P, P, P, I64, C.c_uint64, P, P, P, C.POINTER(C.c_double)]),
+            "w2v_model_score": (C.c_int, [P, S, I64, C.c_uint64, P, P, I64, C.POINTER(I64), P,
+                                          C.POINTER(C.c_double)]),
+            "w2v_model_score_file": (C.c_int, [P, S, S, I32, C.c_uint64, P, P, I64, C.POINTER(I64), P,
+                                               C.POINTER(C.c_double)]),
+            "w2v_model_set_heldout": (C.c_int, [P, P, P, I64, C.c_uint64]),
+            "w2v_model_epoch_heldout": (C.c_int, [P, I64, C.POINTER(C.c_double), C.POINTER(I64)]),
         }
         for k, (r, a) in sig.items():
             f = getattr(L, k)
@@ -300,6 +307,65 @@ class Word2Vec:
         out = np.empty(max(int(rows), 0), np.int32)
         self._chk(self.L.w2v_model_word_classes(self.h, int(which), int(n_classes), int(iterations), _p(out)),
                   "word_classes")
+        return out
+
+    # sentence scores -------------------------------------------------------
+    _COUNTS = ("sentences", "words", "centers", "contexts", "targets", "draws", "nonfinite")
+
+    def _scores(self, call, n_sent, what):
+        """Run one of the score calls; n_sent None = learn the count first (a call without output arrays)."""
+        counts, total, n = np.zeros(7, np.int64), C.c_double(), C.c_int64()
+        if n_sent is None:
+            self._chk(call(None, None, 0, C.byref(n), _p(counts), C.byref(total)), what)
+            n_sent = n.value
+        ll, tg = np.zeros(n_sent, np.float64), np.zeros(n_sent, np.int64)
+        self._chk(call(_p(ll), _p(tg), n_sent, C.byref(n), _p(counts), C.byref(total)), what)
+        out = {"ll": ll, "targets": tg, "summary": dict(zip(self._COUNTS, (int(c) for c in counts)))}
+        out["summary"]["ll"] = total.value
+        out["per_target"] = total.value / int(counts[4]) if counts[4] else 0.0
+        return out
+
+    def score_ids(self, ids, offsets, key=0):
+        """Word2Vec::score_ids: the log-likelihood of each sentence (token ids) under the model's matrices, on
+        the GPU: {"ll", "targets", "summary", "per_target"} (include/Word2Vec.h, include/w2v_dev.h)."""
+        ids = np.ascontiguousarray(ids, np.int32)
+        off = np.ascontiguousarray(offsets, np.int64)
+        if off.size < 1:
+            raise ValueError("score_ids: offsets must hold n_sentences + 1 entries")
+        k = int(key) & ((1 << 64) - 1)
+        return self._scores(lambda ll, tg, cap, n, c, t: self.L.w2v_model_score_ids(
+            self.h, _p(ids), _p(off), off.size - 1, k, ll, tg, c, t), off.size - 1, "score_ids")
+
+    def score(self, sentences, key=0):
+        """Word2Vec::score: sentences of words; out-of-vocabulary words drop out as in training."""
+        t, k = _text(sentences), int(key) & ((1 << 64) - 1)
+        return self._scores(lambda ll, tg, cap, n, c, s: self.L.w2v_model_score(
+            self.h, t, len(t), k, ll, tg, cap, n, c, s), len(sentences), "score")
+
+    def score_file(self, path, format="lines", threads=0, key=0):
+        """Word2Vec::score_file: the sentences file_samples reads from a corpus file."""
+        k = int(key) & ((1 << 64) - 1)
+        return self._scores(lambda ll, tg, cap, n, c, s: self.L.w2v_model_score_file(
+            self.h, str(path).encode(), format.encode(), int(threads), k, ll, tg, cap, n, c, s), None, "score_file")
+
+    def set_heldout(self, ids=None, offsets=None, key=0):
+        """Word2Vec::heldout_ids / heldout_offsets: scored after every epoch of a single-device train
+        (None = off); read the results with epoch_heldout."""
+        k = int(key) & ((1 << 64) - 1)
+        if ids is None or offsets is None:
+            self._chk(self.L.w2v_model_set_heldout(self.h, None, None, 0, k), "set_heldout")
+            return
+        ids = np.ascontiguousarray(ids, np.int32)
+        off = np.ascontiguousarray(offsets, np.int64)
+        self._chk(self.L.w2v_model_set_heldout(self.h, _p(ids), _p(off), off.size - 1, k), "set_heldout")
+
+    @property
+    def epoch_heldout(self) -> list:
+        """[(ll, targets)] per epoch of the last train call (empty without set_heldout, and with replicas)."""
+        out = []
+        ll, tg = C.c_double(), C.c_int64()
+        while self.L.w2v_model_epoch_heldout(self.h, len(out), C.byref(ll), C.byref(tg)) == 0:
+            out.append((ll.value, tg.value))
         return out
 
     # introspection ---------------------------------------------------------
