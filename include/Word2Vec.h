@@ -348,6 +348,7 @@ class Word2Vec {
   bool uses_C() const;
   void check_score_args(const std::vector<int32_t>& ids, const std::vector<int64_t>& offsets, const char* what) const;
   void check_limits() const;
+  void check_heldout() const;  // the held-out set of a single-device train: refused before the weights are touched
   void finish_vocab(std::unordered_map<std::string, int>& tally);
   void ensure_device();
   void upload_vocab_products();

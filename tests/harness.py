@@ -13,11 +13,29 @@ MODES = {
     "cbow_hs": dict(model="cbow", train_method="hs", negative=0),
 }
 
+# Hierarchical softmax together with negative sampling: both updates per target
+# (Word2Vec.cpp:304-311, :342-349). Kept out of MODES, which parametrises the
+# golden-keyed quality tests.
+COMBINED_MODES = {
+    "sg_hsns": dict(model="sg", train_method="hs", negative=5),
+    "cbow_hsns": dict(model="cbow", train_method="hs", negative=5),
+}
+
+
+def mode_config(mode: str, negative=None):
+    """The entry of MODES or COMBINED_MODES; `negative` overrides its draw
+    count (only for a mode that draws negatives)."""
+    m = dict(MODES[mode] if mode in MODES else COMBINED_MODES[mode])
+    if negative is not None:
+        assert m["negative"] > 0 and negative > 0, (mode, negative)
+        m["negative"] = negative
+    return m
+
 
 def oracle_run(sentences, mode: str, dim=32, window=5, iters=1, seed=1234, min_count=2,
                table_size=100_000, subsample=1e-3, cbow_mean=True, init_alpha=0.05, min_alpha=2.5e-6,
-               train=True):
-    m = MODES[mode]
+               train=True, negative=None):
+    m = mode_config(mode, negative)
     o = Oracle(iter=iters, window=window, min_count=min_count, table_size=table_size, word_dim=dim,
                negative=m["negative"], subsample_threshold=subsample, init_alpha=init_alpha,
                min_alpha=min_alpha, cbow_mean=cbow_mean, train_method=m["train_method"], model=m["model"])
@@ -30,10 +48,11 @@ def oracle_run(sentences, mode: str, dim=32, window=5, iters=1, seed=1234, min_c
     return o
 
 
-def device_config(o: Oracle, mode: str, dim, window, iters, table_size, cbow_mean, init_alpha, min_alpha):
+def device_config(o: Oracle, mode: str, dim, window, iters, table_size, cbow_mean, init_alpha, min_alpha,
+                  negative=None):
     from word2vec_amd.device import Config
 
-    m = MODES[mode]
+    m = mode_config(mode, negative)
     return Config(word_dim=dim, window=window, negative=m["negative"], hs=m["train_method"] == "hs",
                   cbow=m["model"] == "cbow", cbow_mean=cbow_mean, iter=iters, init_alpha=init_alpha,
                   min_alpha=min_alpha, table_size=table_size)

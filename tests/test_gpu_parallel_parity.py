@@ -17,7 +17,7 @@ import pytest
 
 from tests.corpus import zipf_sentences
 from tests.harness import (MODES, bound_device_from_oracle, check_parity, device_config, device_from_oracle,
-                           oracle_run)
+                           mode_config, oracle_run)
 
 # Bounds: test_gpu_parity.py's measured multi-sentence bound MULTI (2e-5 norm-
 # wise, 2e-3 per element), LIFTED (2e-5 / 5e-3) for rows past 512 floats as
@@ -137,7 +137,7 @@ def _check_path(ref, mode, plan, pol, st, priv_n, ctx_n, deep, tag):
     assert (plan["priv_sc"] == 1.0).all() and (plan["ctx_sc"] == 1.0).all()
     assert plan["hs_hot_avg"] == 0 and plan["hot_sc"].size == 0
     assert plan["deep"] == deep and pol["deep"] == deep, (plan["deep"], deep)
-    if MODES[mode]["train_method"] == "hs" and priv_n > 0:
+    if mode_config(mode)["train_method"] == "hs" and priv_n > 0:
         assert plan["priv_lo"] == ref["V"] - 1 - priv_n  # the nodes nearest the root
     elif priv_n > 0:
         assert plan["priv_lo"] == 0
@@ -192,7 +192,7 @@ def _auto_rows(mode, dim):
 
 
 def _hs(mode):
-    return MODES[mode]["train_method"] == "hs"
+    return mode_config(mode)["train_method"] == "hs"
 
 
 # 1. Default policy: the automatic ranges with an LDS budget that holds them

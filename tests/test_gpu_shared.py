@@ -25,9 +25,10 @@ pytestmark = pytest.mark.gpu
 KEY = 0x0DDC_0FFE_E0DD_F00D
 
 
-def _oracle(sents, dim, window=5, negative=15, table_size=100_000, subsample=1e-3, alpha=0.05, iters=1):
+def _oracle(sents, dim, window=5, negative=15, table_size=100_000, subsample=1e-3, alpha=0.05, iters=1,
+            min_alpha=2.5e-6):
     o = Oracle(iter=iters, window=window, min_count=2, table_size=table_size, word_dim=dim, negative=negative,
-               subsample_threshold=subsample, init_alpha=alpha, min_alpha=2.5e-6, cbow_mean=True,
+               subsample_threshold=subsample, init_alpha=alpha, min_alpha=min_alpha, cbow_mean=True,
                train_method="ns", model="sg")
     o.load_sentences(sents)
     o.seed(1234)
@@ -40,16 +41,16 @@ def _oracle(sents, dim, window=5, negative=15, table_size=100_000, subsample=1e-
     o.set_matrix(1, ((rng.random((o.V, dim)) - 0.5) / dim).astype(np.float32))
     o.set_shared_negatives(True)
     cfg = Config(word_dim=dim, window=window, negative=negative, hs=False, cbow=False, cbow_mean=True, iter=iters,
-                 init_alpha=alpha, min_alpha=2.5e-6, table_size=table_size)
+                 init_alpha=alpha, min_alpha=min_alpha, table_size=table_size)
     return o, cfg
 
 
 def _setup(sents, dim, window=5, negative=15, table_size=100_000, subsample=1e-3, alpha=0.05, pitch=None,
-           iters=1):
+           iters=1, min_alpha=2.5e-6):
     """The oracle and a sequential-schedule handle on its matrices; `pitch`:
     the matrices as caller-owned torch tensors of that row pitch (bind_model),
     returned as d.bound."""
-    o, cfg = _oracle(sents, dim, window, negative, table_size, subsample, alpha, iters)
+    o, cfg = _oracle(sents, dim, window, negative, table_size, subsample, alpha, iters, min_alpha)
     if pitch is None:
         d = device_from_oracle(o, cfg, initial=False)
     else:

@@ -3,6 +3,7 @@
 // vector/vocab files, and the C bridge's argument checks) with no device call,
 // for the AddressSanitizer / UndefinedBehaviorSanitizer build
 // (make -C word2vec_amd/csrc asan; tests/test_host_sanitizers.py).
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -189,6 +190,28 @@ int main(int argc, char** argv) {
     w.negative = 64;
     expect(refused({0, 1}, {0, 2}), "score_ids: negative past the scoring limit");
     w.negative = 5;
+    {  // hs together with negative > 0: refused by score_ids, and by train with a (valid) held-out set
+      w.train_method = "hs";
+      expect(refused({0, 1}, {0, 2}), "score_ids: hs together with negative > 0");
+      w.heldout_ids = {0, 1};
+      w.heldout_offsets = {0, 2};
+      std::vector<int32_t> ids{0, 1};
+      std::vector<int64_t> off{0, 2};
+      const std::vector<float> w0(w.W.data(), w.W.data() + (size_t)w.W.rows() * (size_t)w.W.cols());
+      bool threw = false;
+      try {
+        w.train_ids(ids, off, 2);
+      } catch (const std::invalid_argument& e) {
+        threw = std::string(e.what()).find("no single objective") != std::string::npos;
+      }
+      expect(threw, "train: hs together with negative > 0 and a held-out set is refused before any device call");
+      expect(w0.size() == (size_t)w.W.rows() * (size_t)w.W.cols() && w0.size() > 0 &&
+                 std::equal(w0.begin(), w0.end(), w.W.data()),
+             "train: a refused held-out set leaves the weights as init_weights set them");
+      w.train_method = "ns";
+      w.heldout_ids.clear();
+      w.heldout_offsets.clear();
+    }
     w.W.resize(1, 16);
     expect(refused({0, 1}, {0, 2}), "score_ids: matrices of another shape");
     w.heldout_ids = {0, V};

@@ -500,7 +500,7 @@ void Word2Vec::run_epochs(const std::vector<int32_t>& ids, const std::vector<int
     run_epochs_replicas(ids, offsets, train_words);
     return;
   }
-  if (!heldout_ids.empty()) check_score_args(heldout_ids, heldout_offsets, "heldout");
+  check_heldout();
   ensure_device();
   upload_vocab_products();
   check(w2v_dev_upload_model(dev_, W.data(), uses_C() ? C.data() : nullptr,
@@ -790,6 +790,7 @@ void Word2Vec::check_limits() const {
 void Word2Vec::train(std::vector<std::vector<std::string>>& sentences) {
   if (phrase) throw std::invalid_argument("word2vec_amd: phrase mode reads files (train_file); train(sentences) does not detect phrases");
   check_limits();
+  check_heldout();
   drop_index();
   if (!resume_) init_weights(vocab.size());
   int64_t train_words = 0;
@@ -809,6 +810,7 @@ void Word2Vec::train(std::vector<std::vector<std::string>>& sentences) {
 void Word2Vec::train_ids(const std::vector<int32_t>& ids, const std::vector<int64_t>& offsets,
                          int64_t train_words) {
   check_limits();
+  check_heldout();
   drop_index();
   if (!resume_) init_weights(vocab.size());
   run_epochs(ids, offsets, train_words);
@@ -817,8 +819,9 @@ void Word2Vec::train_ids(const std::vector<int32_t>& ids, const std::vector<int6
 // ---------------------------------------------------------------------------
 // Sentence scores (additive; include/w2v_dev.h, w2v_dev_score).
 // ---------------------------------------------------------------------------
-// What the host can check without a device: the arrays' shape, the ids' range
-// and that the matrices the objective reads match the vocabulary.
+// What the host can check without a device: the arrays' shape, the ids' range,
+// that the matrices the objective reads match the vocabulary, and that the
+// configuration has an objective to score.
 void Word2Vec::check_score_args(const std::vector<int32_t>& ids, const std::vector<int64_t>& offsets,
                                 const char* what) const {
   auto bad = [&](const std::string& why) { throw std::invalid_argument(std::string("word2vec_amd: ") + what + ": " + why); };
@@ -834,6 +837,17 @@ void Word2Vec::check_score_args(const std::vector<int32_t>& ids, const std::vect
   if (word_dim < 1 || word_dim > md) bad("word_dim must be in [1, " + std::to_string(md) + "]");
   if (window < 0 || window > mw) bad("window must be in [0, " + std::to_string(mw) + "] to score");
   if (negative < 0 || negative > mn) bad("negative must be in [0, " + std::to_string(mn) + "] to score");
+  // w2v_dev_score refuses this too, but train() reaches it only after its first
+  // epoch: a held-out set must be refused before anything trains
+  if (train_method == "hs" && negative > 0) bad("hs together with negative > 0 has no single objective");
+}
+
+// train() scores heldout_ids after every epoch of a single-device run (with
+// replicas it does not: Word2Vec.h). A set it could not score is refused
+// before train() re-initialises the weights, so a refused call changes nothing.
+void Word2Vec::check_heldout() const {
+  if (gpu_devices.size() > 1 || heldout_ids.empty()) return;
+  check_score_args(heldout_ids, heldout_offsets, "heldout");
 }
 
 double Word2Vec::score_ids(const std::vector<int32_t>& ids, const std::vector<int64_t>& offsets,
