@@ -315,6 +315,22 @@ def test_replay_wide_window(mode, window):
     check_parity(got, want, init, *MULTI, tag=f"wide replay {mode} w{window}")
 
 
+@pytest.mark.parametrize("mode", ["cbow_ns", "cbow_hs"])
+@pytest.mark.parametrize("window", [31, 32])
+def test_replay_cbow_widest_lane_window(mode, window):
+    """The two sides of the CBOW kernels' window threshold: window 31 is the
+    widest the one-position-per-lane form takes (a span of 63 positions), window
+    32 the narrowest of the four-per-lane form (65). Every sentence has 150
+    tokens and min_count 1 drops none, so a center whose shrink draw is 0 has
+    the full span (the shrink is uniform over [0, window): of the 472 centers
+    that survive subsampling, 10 have a span of 63 at window 31 and 9 a span of
+    65 at window 32, read off the recorded stream)."""
+    sents = zipf_sentences(8, 150, 150, seed=27)
+    assert min(len(s) for s in sents) >= 70
+    got, want, init = _run_replay(mode, sents, dim=48, window=window, iters=1, table_size=10_000, min_count=1)
+    check_parity(got, want, init, *MULTI, tag=f"lane-window replay {mode} w{window}")
+
+
 @pytest.mark.parametrize("mode", ["sg_ns", "cbow_ns", "cbow_hs"])
 def test_philox_sequential_wide_window(mode):
     sents = zipf_sentences(6, 300, 150, seed=23, ragged=True)

@@ -223,7 +223,7 @@ namespace {
 using KernelFn = w2v::KernelFn;
 
 // Instantiated row widths (floats per lane): the smallest one covering d
-// (w2v_kernels.hpp kFullVecs relies on it: the vectors below the next smaller
+// (w2v_rows.hpp kFullVecs relies on it: the vectors below the next smaller
 // width are inside d in every lane).
 const w2v::NvKernels& kernels_for_need(int need) {
   for (const w2v::NvKernels& k : w2v::kNvKernels)
@@ -356,7 +356,7 @@ int w2v_dev_create(const w2v_dev_config* cfg, w2v_dev** out) {
   }
   h->d4 = (cfg->word_dim + 3) & ~3;
   h->nv = pick_nv(cfg->word_dim);
-  h->pitch = (int64_t)h->nv * w2v::kWave;  // the kernels' row width (w2v_kernels.hpp, Row I/O)
+  h->pitch = (int64_t)h->nv * w2v::kWave;  // the kernels' row width (w2v_rows.hpp)
   h->need_C = cfg->negative > 0 || cfg->cbow;
   h->need_S = cfg->hs != 0;
   *out = h;

@@ -1,5 +1,5 @@
 // One row width's kernel instantiations (built once per W2V_NV by the
-// Makefile so the 9 widths compile in parallel); w2v_dev.hip dispatches.
+// Makefile so the 11 widths compile in parallel); w2v_dev.hip dispatches.
 #include "w2v_kernels.hpp"
 #include "w2v_launch.hpp"
 

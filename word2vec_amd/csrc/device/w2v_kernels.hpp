@@ -44,6 +44,9 @@
 #include <stdint.h>
 
 #include "w2v_limits.hpp"
+#include "w2v_philox.hpp"
+#include "w2v_rows.hpp"
+#include "w2v_wave.hpp"
 
 namespace w2v {
 
@@ -130,68 +133,22 @@ struct Counters {
 // batch (batch_grad_l).
 constexpr int kNonFinite = 5;
 
-// ---------------------------------------------------------------------------
-// Wave primitives
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ int lane_id() { return (int)__lane_id(); }
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
+// One wave's counts into the launch's statistics (called by one lane).
+__device__ __forceinline__ void report_counters(const TrainArgs& a, const Counters& cnt) {
+  atomicAdd(&a.stats[0], cnt.centers);
+  atomicAdd(&a.stats[1], cnt.contexts);
+  atomicAdd(&a.stats[2], cnt.targets);
+  atomicAdd(&a.stats[3], cnt.draws);
+  atomicAdd(&a.stats[4], cnt.sentences);
 }
 
-// Full-wave sum, broadcast to every lane (all 64 lanes must be active).
-__device__ __forceinline__ float wave_sum(float v) {
-  v += dpp_f<0xb1>(v);   // quad_perm [1,0,3,2]
-  v += dpp_f<0x4e>(v);   // quad_perm [2,3,0,1]
-  v += dpp_f<0x124>(v);  // row_ror:4
-  v += dpp_f<0x128>(v);  // row_ror:8
-  v += dpp_f<0x142>(v);  // row_bcast:15
-  v += dpp_f<0x143>(v);  // row_bcast:31
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
-
-__device__ __forceinline__ int readlane_i(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
-__device__ __forceinline__ int uniform_i(int v) { return __builtin_amdgcn_readfirstlane(v); }
-
-__device__ __forceinline__ unsigned long long ballot(bool p) { return __ballot(p); }
-
-// Wait until this wave's outstanding memory operations (incl. no-return atomics) completed.
-__device__ __forceinline__ void drain_vmem() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
-// ---------------------------------------------------------------------------
-// Philox4x32-10 (Salmon et al. SC'11), the throughput-mode RNG.
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ void philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                       uint32_t k0, uint32_t k1, uint32_t& o0, uint32_t& o1,
-                                       uint32_t& o2, uint32_t& o3) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-    c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  o0 = c0; o1 = c1; o2 = c2; o3 = c3;
-}
-
-// libstdc++ generate_canonical<float,24> of one 32-bit draw.
-__device__ __forceinline__ float canonical_f(uint32_t x) {
-  float r = (float)x * (1.0f / 4294967296.0f);
-  return r >= 1.0f ? __int_as_float(0x3F7FFFFF) : r;
-}
-
-// Draw k of context slot `slot`: counter (position, sentence, slot << 8 | k's
-// low byte, epoch ^ (k's high bits << 20)); for k < 256 (every negative up to
-// 255) the last word is the epoch alone.
-__device__ __forceinline__ uint32_t philox_table_pos(const TrainArgs& a, uint32_t s, uint32_t i,
-                                                     uint32_t slot, uint32_t k) {
-  uint32_t o0, o1, o2, o3;
-  philox(i, s, (slot << 8) | (k & 255u), a.epoch ^ ((k >> 8) << 20), a.key0, a.key1, o0, o1, o2, o3);
-  const uint64_t x = ((uint64_t)o1 << 32) | o0;
-  return (uint32_t)__umul64hi(x, (uint64_t)a.table_size);
+// The learning rate from the shared word counter (Word2Vec.cpp:379-380),
+// floored at min_alpha. The double arithmetic and its operand order are the
+// reference's: part of the parity.
+__device__ __forceinline__ float scheduled_alpha(const TrainArgs& a) {
+  const unsigned long long cw = __hip_atomic_load(a.words, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const float al = (float)(a.init_alpha * (1.0 - 1.0 / a.iter * (double)cw / a.train_words));
+  return (a.min_alpha < al) ? al : a.min_alpha;
 }
 
 // ---------------------------------------------------------------------------
@@ -241,75 +198,6 @@ __device__ __forceinline__ PrivRows ctx_rows(const TrainArgs& a, float* lds) {
   p.n = a.ctx_n;
   p.ctx = true;
   return p;
-}
-
-// ---------------------------------------------------------------------------
-// Row I/O: a row is NV floats per lane, element lane + 64 v (v < NV). Rows
-// are NV * 64 floats apart at least (pitch >= NV * 64, w2v_dev_bind_model)
-// and their columns past word_dim are zero, and stay zero: every delta there
-// is g * 0. So every lane loads, stores and adds its whole row, with no
-// per-element guard: no exec-mask branches around the memory instructions
-// (an exec-masked zero-fill of a register whose load may be outstanding made
-// the compiler wait for ALL this wave's memory operations — vmcnt(0), stores
-// and memory-side atomics included — before every hot row's gather), and
-// every store writes whole 128-B lines. The dot products add the padding's
-// zeros, so the sums are bit-identical to the guarded form.
-// ---------------------------------------------------------------------------
-template <int NV>
-__device__ __forceinline__ void load_row(const float* M, int64_t row, int64_t pitch, int lane, bool fresh,
-                                         float (&r)[NV]) {
-  const float* p = M + row * pitch + lane;
-  if (fresh) {  // agent-scope relaxed loads: global_load_dword sc1, bypass the CU's L1
-#pragma unroll
-    for (int v = 0; v < NV; ++v) r[v] = __hip_atomic_load(p + kWave * v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  } else {
-#pragma unroll
-    for (int v = 0; v < NV; ++v) r[v] = p[kWave * v];
-  }
-}
-
-template <int NV>
-__device__ __forceinline__ void store_row(float* M, int64_t row, int64_t pitch, int lane, const float (&r)[NV]) {
-  float* p = M + row * pitch + lane;
-#pragma unroll
-  for (int v = 0; v < NV; ++v) p[kWave * v] = r[v];
-}
-
-// row += delta, memory-side (no-return global_atomic_add_f32, 256 contiguous B
-// per instruction). The padding lanes are masked here: an atomic has no
-// destination register (nothing to zero-fill, no wait), and a memory-side add
-// of 0 would still cost the atomic unit a request (d 300: 320 adds per row
-// instead of 300; measured 2.5 % of configs[2], profiles/r03d_guards_ab.log).
-// Vectors of a row every lane of which is inside word_dim: pick_nv
-// (w2v_dev.hip) takes the smallest row width >= ceil(d / 64) of {1, 2, 3, 4,
-// 5, 6, 8, 12, 16, 24, 32}, so d > 64 x the next smaller width and those
-// vectors need no lane mask (a mask is an exec-mask round trip per atomic).
-template <int NV>
-constexpr int kFullVecs = NV <= 6 ? NV - 1 : NV == 8 ? 6 : NV == 12 ? 8 : NV == 16 ? 12 : NV == 24 ? 16 : 24;
-
-template <int NV>
-__device__ __forceinline__ void atomic_add_row(float* M, int64_t row, int64_t pitch, int d, int lane,
-                                               const float (&delta)[NV]) {
-  float* p = M + row * pitch + lane;
-#pragma unroll
-  for (int v = 0; v < NV; ++v)
-    if (v < kFullVecs<NV> || lane + kWave * v < d)
-      (void)__hip_atomic_fetch_add(p + kWave * v, delta[v], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// M[row] += delta: atomically for hot rows; else read-modify-write (Hogwild).
-template <int NV>
-__device__ __forceinline__ void add_to_row(float* M, int64_t row, bool hot, int64_t pitch, int d, int lane,
-                                           const float (&delta)[NV]) {
-  if (hot) {
-    atomic_add_row<NV>(M, row, pitch, d, lane, delta);
-  } else {
-    float cur[NV];
-    load_row<NV>(M, row, pitch, lane, false, cur);
-#pragma unroll
-    for (int v = 0; v < NV; ++v) cur[v] += delta[v];
-    store_row<NV>(M, row, pitch, lane, cur);
-  }
 }
 
 // A privatised row's value is the global row plus this workgroup's pending delta.
@@ -382,82 +270,6 @@ __device__ __forceinline__ float grad_of(float fl, int cl, float alpha) {
   return ((float)(1 - cl) - ns_sigmoid(e)) * alpha;
 }
 
-// ---------------------------------------------------------------------------
-// The dot products of a batch of targets, reduced together. One wave_sum per
-// target would cost 6 DPP adds + a readlane each, and gathering the sums back
-// into lanes for the batch's sigma step 2 selects + a readlane per target:
-// ~13 VALU per target on a kernel that at d = 100 keeps the VALU busy ~77 % of
-// its cycles (profiles/r04c_c1_pmc_counters.json: SQ_ACTIVE_INST_VALU /
-// SQ_WAVE_CYCLES per SIMD). Instead the NB (4 or 8) per-lane partials are
-// folded pairwise, halving the vector count at each step:
-//   xor 32  v_permlane32_swap(a, b): a = [a.lo | b.lo], b = [a.hi | b.hi];
-//           a + b holds a's half-sums in lanes 0-31 and b's in lanes 32-63
-//   xor 16  v_permlane16_swap (odd rows of the first operand with even rows
-//           of the second): rows of a + b = [a, b, a', b'] sums
-//   xor 8   keep / give selected by lane bit 3 plus a row_ror:8 DPP add
-//   xor 4, 2, 1 (one vector left): quad_perm and row_half_mirror DPP adds
-// so each group of 8 lanes (NB = 4: of 16) ends with one target's total:
-// 18 VALU for 8 targets instead of ~104. The lanes of a group hold identical
-// bits (a + b == b + a). Only the order of the 64-term sum changes.
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ void swap32(float& a, float& b) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-  a = __uint_as_float(r[0]);
-  b = __uint_as_float(r[1]);
-}
-__device__ __forceinline__ void swap16(float& a, float& b) {
-  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-  a = __uint_as_float(r[0]);
-  b = __uint_as_float(r[1]);
-}
-// 16-lane row r of a permlane16-folded vector holds pair member
-// ((r & 1) << 1) | (r >> 1) (rows 0..3: members 0, 2, 1, 3; an involution).
-__host__ __device__ constexpr int row_member(int r) { return ((r & 1) << 1) | (r >> 1); }
-template <int N>
-constexpr int kBatchN = N <= 4 ? 4 : 8;
-// The first lane of target t's group after batch_dots<N>.
-template <int N>
-__device__ __forceinline__ constexpr int batch_lane(int t) {
-  return kBatchN<N> == 8 ? 16 * row_member(t & 3) + 8 * (t >> 2) : 16 * row_member(t);
-}
-// The target whose total lane `lane` holds after batch_dots<N>.
-template <int N>
-__device__ __forceinline__ int batch_target(int lane) {
-  return kBatchN<N> == 8 ? 4 * ((lane >> 3) & 1) + row_member(lane >> 4) : row_member(lane >> 4);
-}
-
-template <int N>
-__device__ __forceinline__ float batch_dots(const float (&p)[N], int lane) {
-  static_assert(N >= 1 && N <= 8, "batch of 1..8 targets");
-  constexpr int NB = kBatchN<N>;
-  float q[NB / 2];
-#pragma unroll
-  for (int k = 0; k < NB / 2; ++k) {  // xor 32
-    float a = 2 * k < N ? p[2 * k] : 0.f, b = 2 * k + 1 < N ? p[2 * k + 1] : 0.f;
-    swap32(a, b);
-    q[k] = a + b;
-  }
-  float r[NB / 4];
-#pragma unroll
-  for (int k = 0; k < NB / 4; ++k) {  // xor 16
-    float a = q[2 * k], b = q[2 * k + 1];
-    swap16(a, b);
-    r[k] = a + b;
-  }
-  float v;
-  if (NB == 8) {  // xor 8: lanes with bit 3 clear keep r[0], set keep r[NB / 4 - 1]
-    const bool hi = (lane & 8) != 0;
-    const float keep = hi ? r[NB / 4 - 1] : r[0], give = hi ? r[0] : r[NB / 4 - 1];
-    v = keep + dpp_f<0x128>(give);  // row_ror:8 (a lane 8 apart: the other bit-3 half)
-  } else {
-    v = r[0] + dpp_f<0x128>(r[0]);
-  }
-  v += dpp_f<0xb1>(v);   // quad_perm [1,0,3,2]
-  v += dpp_f<0x4e>(v);   // quad_perm [2,3,0,1]
-  v += dpp_f<0x141>(v);  // row_half_mirror: the other quad of the 8
-  return v;
-}
-
 // g of a batch in batch_dots' layout: lane L evaluates target batch_target(L)
 // (its code, held in lane c0 + t of code_l, fetched with one permute); counts
 // the batch's non-finite scores.
@@ -474,19 +286,11 @@ __device__ __forceinline__ float batch_grad_l(float fl, int T, int code_l, int c
   return grad_of<HSF>(fl, cl, alpha);
 }
 
-__device__ __forceinline__ float readlane_f(float v, int l) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
-
 // A batch of N > 8 targets (the deep HS pipeline of the low-occupancy
 // kernel, train_epoch_deep_kernel) in groups of 8: group h's dots are folded
 // and evaluated exactly as a batch of 8 would be (batch_dots / batch_grad_l),
 // so each target's sum, sigma and g are the bits a batch of <= 8 gives. For N
 // <= 8 this is the single batch_dots + batch_grad_l of before.
-template <int N>
-constexpr int kGroups = (N + 7) / 8;
-template <int N>
-constexpr int kGroupN = N < 8 ? N : 8;
 template <int N, bool HSF>
 __device__ __forceinline__ void batch_g(const float (&pd)[N], int T, int code_l, int c0, float alpha, int lane,
                                         unsigned long long* stats, float (&gl)[kGroups<N>]) {
@@ -511,6 +315,9 @@ __device__ __forceinline__ float batch_gt(const float (&gl)[kGroups<N>], int t) 
 // row and code (HS: Huffman code; NS: 1 - label). Rows are gathered together,
 // then updated in target order so grad accumulates in the reference's order.
 // Rows in [hot_lo, hot_hi) take the atomic path.
+// Not written as hs_gather + hs_score + hs_apply: that keeps every gt[t] live across the batch, and at
+// row width 5 took the skip-gram NS kernel from 115 VGPRs and no scratch to 128 VGPRs and 72 B of scratch
+// per lane (the other NS kernels spilled too). Here each gt is used at once.
 // ---------------------------------------------------------------------------
 template <int NV, int MAXT, bool HSF>
 __device__ __forceinline__ void apply_targets(float* M, int64_t pitch, int d, int lane, int T, int row_l,
@@ -590,8 +397,7 @@ __device__ __forceinline__ void flush_private(const TrainArgs& a, const PrivRows
   for (int w = 0; w < 2; ++w) {
     unsigned long long m = 0;
     if (lane == 0 && 64 * w < pr.n) m = atomicExch(pr.dirty + w, 0ull);
-    mw[w] = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(m >> 32)) << 32) |
-            (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)m);
+    mw[w] = uniform_u64(m);
   }
   for (int w = 0; w < 2; ++w)
   for (unsigned long long m = mw[w]; m;) {
@@ -729,27 +535,6 @@ __device__ __forceinline__ void hs_word(const TrainArgs& a, int word, int lane, 
   }
 }
 
-// NS target list of positive `word` against `negw_l` lanes [base, base + neg):
-// lane t of tgt_l holds target t (positive first, then first occurrences of
-// the negatives that differ from it — the set semantics of
-// Word2Vec.cpp:253-257); returns the count.
-__device__ __forceinline__ int ns_targets(int neg, int word, int negw_l, int base, int lane, int& tgt_l) {
-  const int nk = __shfl(negw_l, (base + lane) & (kWave - 1));
-  bool dup = (lane >= neg) || (nk == word);
-  for (int j = 0; j < neg - 1; ++j) {
-    const int v = readlane_i(nk, j);
-    dup = dup || (lane > j && nk == v);
-  }
-  const unsigned long long uniq = ballot(!dup);
-  // compaction in one forward permute: the k-th unique draw (in lane order)
-  // goes to lane 1 + k; duplicates to lane 0, which then takes the positive
-  // (a walk over the set bits cost ~4 VALU + 6 SALU per target)
-  const int k = __builtin_amdgcn_mbcnt_hi((unsigned)(uniq >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)uniq, 0u));
-  const int v = __builtin_amdgcn_ds_permute((dup ? 0 : 1 + k) << 2, nk);
-  tgt_l = (lane == 0) ? word : v;
-  return 1 + __popcll(uniq);
-}
-
 // The T targets of tgt_l / code_l, MAXT rows per batch.
 template <int NV, int MAXT>
 __device__ __forceinline__ void apply_list(const TrainArgs& a, float* M, int T, int tgt_l, int code_l,
@@ -785,18 +570,6 @@ __device__ __forceinline__ void ns_word(const TrainArgs& a, float* M, int word, 
 // targets are applied before the next chunk's are found (a duplicate test
 // needs only the words, not the rows).
 // ---------------------------------------------------------------------------
-template <bool REPLAY>
-__device__ __forceinline__ int draw_chunk(const TrainArgs& a, uint32_t s, uint32_t i, int slot, int ch, int lane,
-                                          const uint32_t* rp) {
-  const int k = kWave * ch + lane;
-  int w = -1;
-  if (k < a.negative) {
-    const uint32_t pos = REPLAY ? rp[k] : philox_table_pos(a, s, i, (uint32_t)slot, (uint32_t)k);
-    w = (int)a.table[pos];
-  }
-  return w;
-}
-
 template <int NV, int MAXT, bool REPLAY>
 __device__ __forceinline__ void ns_word_many(const TrainArgs& a, float* M, int word, uint32_t s, uint32_t i, int slot,
                                           int lane, const float (&x)[NV], float (&g)[NV], float alpha,
@@ -829,26 +602,6 @@ __device__ __forceinline__ void ns_word_many(const TrainArgs& a, float* M, int w
   }
   cnt.draws += (unsigned long long)neg;
   if (REPLAY) rp += neg;
-}
-
-// Draw table words for `ndraw` (slot, k) pairs starting at slot `slot0`:
-// lane t -> slot0 + t / neg, k = t % neg.
-template <bool REPLAY>
-__device__ __forceinline__ int draw_negatives(const TrainArgs& a, uint32_t s, uint32_t i, int slot0, int ndraw,
-                                              int lane, const uint32_t*& rp) {
-  int w = 0;
-  if (lane < ndraw) {
-    uint32_t pos;
-    if (REPLAY) {
-      pos = rp[lane];
-    } else {
-      const int neg = a.negative;
-      pos = philox_table_pos(a, s, i, (uint32_t)(slot0 + lane / neg), (uint32_t)(lane % neg));
-    }
-    w = (int)a.table[pos];
-  }
-  if (REPLAY) rp += ndraw;
-  return w;
 }
 
 // ---------------------------------------------------------------------------
@@ -1018,16 +771,6 @@ __device__ __forceinline__ void cbow_center(const TrainArgs& a, float* lds, cons
                                       cnt, lane);
 }
 
-// Lane-register arrays of NCH x 64 positions: element j is lane j % 64 of register j / 64.
-template <int NCH>
-__device__ __forceinline__ int pick_lane(const int (&v)[NCH], int j) {
-  int r = 0;
-#pragma unroll
-  for (int ch = 0; ch < NCH; ++ch)
-    if (ch == (j >> 6)) r = readlane_i(v[ch], j & (kWave - 1));
-  return r;
-}
-
 // CBOW center for windows wider than a wave (2 * window + 1 > 64, window <=
 // 32 * NCH - 1): the same set semantics and visiting order as cbow_center, the
 // span's positions held NCH per lane (position lo + 64 ch + lane).
@@ -1135,19 +878,17 @@ __device__ __forceinline__ void cbow_center_huge(const TrainArgs& a, float* lds,
     }
   }
   drain_vmem();
+  const auto mask_of = [&](int ch) {  // chunk ch's unique mask, as pass 1 left it
+    return ((unsigned long long)(uint32_t)__hip_atomic_load(masks + 2 * ch + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) << 32) |
+           (uint32_t)__hip_atomic_load(masks + 2 * ch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  };
   for (int ch = 0; ch < nch; ++ch) {
     const int p = kWave * ch + lane;
     const int id = (p < span) ? sent[lo + p] : -1;
-    const unsigned long long mine =
-        ((unsigned long long)(uint32_t)__hip_atomic_load(masks + 2 * ch + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) << 32) |
-        (uint32_t)__hip_atomic_load(masks + 2 * ch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const bool uniq = (mine >> lane) & 1ull;
+    const bool uniq = (mask_of(ch) >> lane) & 1ull;
     int rank = 0;
     for (int c2 = 0; c2 < nch; ++c2) {
-      unsigned long long m =
-          ((unsigned long long)(uint32_t)__hip_atomic_load(masks + 2 * c2 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) << 32) |
-          (uint32_t)__hip_atomic_load(masks + 2 * c2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      m = ((unsigned long long)(uint32_t)readlane_i((int)(m >> 32), 0) << 32) | (uint32_t)readlane_i((int)(uint32_t)m, 0);
+      unsigned long long m = uniform_u64(mask_of(c2));
       while (m) {
         const int b = __builtin_ctzll(m);
         m &= m - 1;
@@ -1232,9 +973,7 @@ __device__ __forceinline__ void train_epoch(const TrainArgs& a) {
     if (a.fixed_alpha > 0.0f) {
       alpha = a.fixed_alpha;
     } else if (first || (k % 10u) == 0u) {
-      const unsigned long long cw = __hip_atomic_load(a.words, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const float al = (float)(a.init_alpha * (1.0 - 1.0 / a.iter * (double)cw / a.train_words));
-      alpha = (a.min_alpha < al) ? al : a.min_alpha;
+      alpha = scheduled_alpha(a);
       first = false;
     }
     const int64_t base = a.soff[s];
@@ -1260,10 +999,9 @@ __device__ __forceinline__ void train_epoch(const TrainArgs& a) {
         const bool in = ii < seg_hi;
         const int c_l = in ? sent[ii] : 0;
         const float p_l = in ? a.keep[c_l] : 0.f;
-        uint32_t o0, o1, o2, o3;
-        philox((uint32_t)ii, (uint32_t)s, 0xFFFFFFFFu, a.epoch, a.key0, a.key1, o0, o1, o2, o3);
-        const float u_l = canonical_f(o0);
-        const int rw_l = (int)(((uint64_t)o1 * wmax) >> 32);
+        float u_l;
+        int rw_l;
+        subsample_draw(a, (uint32_t)s, (uint32_t)ii, wmax, u_l, rw_l);
         unsigned long long kept = ballot(in && !(p_l < u_l));
         while (kept) {
           const int b = __builtin_ctzll(kept);
@@ -1292,13 +1030,7 @@ __device__ __forceinline__ void train_epoch(const TrainArgs& a) {
            (int)(threadIdx.x / kWave), cnt.centers, cnt.acc[0], cnt.acc[1], cnt.acc[2], cnt.acc[3], cnt.acc[4],
            cnt.acc[5], cnt.acc[6], cnt.acc[7]);
 #endif
-  if (lane == 0) {
-    atomicAdd(&a.stats[0], cnt.centers);
-    atomicAdd(&a.stats[1], cnt.contexts);
-    atomicAdd(&a.stats[2], cnt.targets);
-    atomicAdd(&a.stats[3], cnt.draws);
-    atomicAdd(&a.stats[4], cnt.sentences);
-  }
+  if (lane == 0) report_counters(a, cnt);
 }
 
 template <int NV, int MAXT, bool CBOW, bool HS, bool NS, bool REPLAY, bool WIDE>

@@ -53,8 +53,9 @@
 
 #include "w2v_dev.h"
 #include "w2v_dev_internal.hpp"
+#include "w2v_mfma.hpp"
 #include "w2v_nn_internal.hpp"
-#include "w2v_shared.hpp"
+#include "w2v_wave.hpp"
 
 namespace w2v {
 

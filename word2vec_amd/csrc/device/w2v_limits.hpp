@@ -1,4 +1,4 @@
-// w2v_limits.hpp — the limits the kernels (w2v_kernels.hpp, w2v_shared.hpp)
+// w2v_limits.hpp — the limits the kernels (w2v_kernels.hpp and the headers under it, w2v_shared.hpp)
 // and the launch policy (w2v_policy.cpp) share. No HIP header: the policy is
 // compiled by the host compiler too.
 #pragma once

@@ -7,7 +7,8 @@
 // the predicted word's Huffman path over synapses1, NS takes the predicted word
 // (label 1) and the distinct other words of `negative` Philox table draws
 // (label 0) — the training kernels' row layout, gathers, paths and counters
-// (w2v_kernels.hpp), with epoch 0 and the caller's key.
+// (w2v_kernels.hpp; the shared pieces: w2v_wave.hpp, w2v_philox.hpp,
+// w2v_rows.hpp), with epoch 0 and the caller's key.
 //
 // One wave scores one work item: up to `item` consecutive centers of one
 // sentence, dequeued from a head counter. The input row stays in registers, a
@@ -24,9 +25,12 @@
 #include <string>
 
 #include "w2v_dev_internal.hpp"
-#include "w2v_kernels.hpp"
 #include "w2v_launch.hpp"
+#include "w2v_limits.hpp"
+#include "w2v_philox.hpp"
+#include "w2v_rows.hpp"
 #include "w2v_score.hpp"
+#include "w2v_wave.hpp"
 
 namespace w2v {
 
@@ -102,16 +106,9 @@ __device__ __forceinline__ void score_path(const ScoreArgs& a, int word, const f
   }
 }
 
-// What the draw helpers of w2v_kernels.hpp read of the training arguments.
-__device__ __forceinline__ TrainArgs draw_args(const ScoreArgs& a) {
-  TrainArgs t{};
-  t.negative = a.negative;
-  t.table = a.table;
-  t.table_size = a.table_size;
-  t.key0 = a.key0;
-  t.key1 = a.key1;
-  t.epoch = 0;
-  return t;
+// The training kernels' draws (w2v_philox.hpp) with the caller's key, epoch 0.
+__device__ __forceinline__ DrawArgs draw_args(const ScoreArgs& a) {
+  return DrawArgs{a.table, a.table_size, a.negative, a.key0, a.key1, 0u};
 }
 
 // The span [lo, lo + span) of a center, kWideChunks positions per lane
@@ -125,7 +122,7 @@ __device__ __forceinline__ void load_span(const int32_t* sent, int lo, int span,
 }
 
 template <int NV, bool HS>
-__device__ __forceinline__ void score_sg_center(const ScoreArgs& a, const TrainArgs& da, const int32_t* sent, int len,
+__device__ __forceinline__ void score_sg_center(const ScoreArgs& a, const DrawArgs& da, const int32_t* sent, int len,
                                                 int i, uint32_t s, int lane, ScoreAcc& acc,
                                                 unsigned long long (&cnt)[3]) {
   const int lo = max(0, i - a.window), hi = min(len, i + a.window + 1);
@@ -162,7 +159,7 @@ __device__ __forceinline__ void score_sg_center(const ScoreArgs& a, const TrainA
 }
 
 template <int NV, bool HS>
-__device__ __forceinline__ void score_cbow_center(const ScoreArgs& a, const TrainArgs& da, const int32_t* sent,
+__device__ __forceinline__ void score_cbow_center(const ScoreArgs& a, const DrawArgs& da, const int32_t* sent,
                                                   int len, int i, uint32_t s, int lane, ScoreAcc& acc,
                                                   unsigned long long (&cnt)[3]) {
   constexpr int MT = kScoreT<NV>;
@@ -241,13 +238,13 @@ __device__ __forceinline__ void score_cbow_center(const ScoreArgs& a, const Trai
 template <int NV, bool CBOW, bool HS>
 __global__ __launch_bounds__(kScoreBlock, kScoreMinWaves<NV>) void score_kernel(ScoreArgs a) {
   const int lane = lane_id();
-  const TrainArgs da = draw_args(a);
+  const DrawArgs da = draw_args(a);
   unsigned long long cnt[3] = {0, 0, 0};  // centers, contexts, draws
   unsigned nonfinite = 0;
   for (;;) {
     unsigned long long kk = 0;
     if (lane == 0) kk = atomicAdd(a.ctr + kScoreHead, 1ull);
-    kk = ((unsigned long long)(unsigned)uniform_i((int)(kk >> 32)) << 32) | (unsigned)uniform_i((int)(unsigned)kk);
+    kk = uniform_u64(kk);
     if ((int64_t)kk >= a.n_items) break;
     int64_t s = 0, hi = a.n_sent - 1;  // the last sentence whose first item is <= kk: the item's owner
     while (s < hi) {

@@ -43,12 +43,10 @@
 //     device-coherent (sc1) loads and write-through stores: see rows_rsrc.
 #pragma once
 #include "w2v_kernels.hpp"
+#include "w2v_mfma.hpp"
 
 namespace w2v {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kSnTile = 16;     // MFMA tile edge: context rows, output rows
 constexpr int kSnStride = 20;   // transpose block row stride in floats
 constexpr int kSnRing = 256;    // kept-token ring (holds a 64-center batch, its lookahead and one more block)
 
@@ -91,10 +89,6 @@ struct SnProf {
   __device__ void stamp(int) {}
 #endif
 };
-
-__device__ __forceinline__ f32x4 mfma16x16x4(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 
 // Row traffic of the frequent rows is device-coherent. Per-XCD L2s are not
 // coherent with each other inside a launch (MI355X_MICROARCH.md, XCD): with
@@ -170,10 +164,6 @@ __device__ __forceinline__ void pair_fixup(f32x4& t0, f32x4& t1, int col) {
     t1[e] = __int_as_float(dpp_i<0x128>(__float_as_int(other)));
   }
 }
-
-// Keep this wave's LDS accesses in program order (the LDS unit serves one
-// wave's operations in order; this only stops the compiler reordering them).
-__device__ __forceinline__ void wave_lds_order() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); }
 
 // g of Word2Vec.cpp:263-264 for one (input, output) pair: f = sigma(L) with
 // the reference's rounding (ns_sigmoid), g = (label - f) * alpha.
@@ -460,9 +450,7 @@ __global__ __launch_bounds__(NW * kWave, WAVES_PER_SIMD) void train_shared_neg_k
         if (a.fixed_alpha > 0.0f) {
           alpha0 = a.fixed_alpha;
         } else if (first || ((a.item0 + k) % 10) == 0) {
-          const unsigned long long cw = __hip_atomic_load(a.words, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          const float al = (float)(a.init_alpha * (1.0 - 1.0 / a.iter * (double)cw / a.train_words));
-          alpha0 = (a.min_alpha < al) ? al : a.min_alpha;
+          alpha0 = scheduled_alpha(a);
           first = false;
         }
       }
@@ -487,10 +475,9 @@ __global__ __launch_bounds__(NW * kWave, WAVES_PER_SIMD) void train_shared_neg_k
         const bool in = ii < len;
         const int c_l = in ? sent[ii] : 0;
         const float p_l = in ? a.keep[c_l] : 0.f;
-        uint32_t o0, o1, o2, o3;
-        philox((uint32_t)ii, (uint32_t)s, 0xFFFFFFFFu, a.epoch, a.key0, a.key1, o0, o1, o2, o3);
-        const float u_l = canonical_f(o0);
-        const int rw_l = (int)(((uint64_t)o1 * wmax) >> 32);
+        float u_l;
+        int rw_l;
+        subsample_draw(a, (uint32_t)s, (uint32_t)ii, wmax, u_l, rw_l);
         const bool keep_l = in && !(p_l < u_l);
         const unsigned long long kept = ballot(keep_l);
         if (keep_l) {
@@ -544,13 +531,7 @@ __global__ __launch_bounds__(NW * kWave, WAVES_PER_SIMD) void train_shared_neg_k
            wave, cnt.centers, cnt.sentences, prof.acc[0], prof.acc[1], prof.acc[2], prof.acc[3], prof.acc[4],
            prof.acc[5], prof.acc[6], prof.acc[7]);
 #endif
-  if (threadIdx.x == 0) {  // every wave counted the same centers; wave 0 reports
-    atomicAdd(&a.stats[0], cnt.centers);
-    atomicAdd(&a.stats[1], cnt.contexts);
-    atomicAdd(&a.stats[2], cnt.targets);
-    atomicAdd(&a.stats[3], cnt.draws);
-    atomicAdd(&a.stats[4], cnt.sentences);
-  }
+  if (threadIdx.x == 0) report_counters(a, cnt);  // every wave counted the same centers; wave 0 reports
 }
 
 }  // namespace w2v
