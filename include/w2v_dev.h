@@ -76,9 +76,14 @@ typedef struct w2v_dev_config {
 typedef struct w2v_dev_stats {
   int64_t words;     /* in-vocab tokens consumed: the reference's current_words
                         increments (Word2Vec.cpp:392-393)                        */
-  int64_t centers;   /* centers kept by subsampling (Word2Vec.cpp:282,332)       */
+  int64_t centers;   /* centers kept by subsampling (Word2Vec.cpp:282,332) whose
+                        shrunk window holds another position: a kept token with
+                        an empty window (a one-token sentence) moves no row and
+                        is not counted, in any mode (as w2v_dev_score counts)    */
   int64_t contexts;  /* SG: (center, context) pairs; CBOW: unique context rows   */
-  int64_t targets;   /* output rows updated: NS targets + HS path nodes          */
+  int64_t targets;   /* output rows updated: per NS call the positive + the
+                        distinct draws that differ from it, per HS call the
+                        path's nodes                                             */
   int64_t draws;     /* unigram-table draws (Word2Vec.cpp:255)                   */
   int64_t sentences; /* sentences processed                                      */
   int64_t nonfinite; /* sigma arguments (row . input) that were not finite: the

@@ -90,6 +90,8 @@ class TrainRef:
                 continue
             lo, hi = max(0, i - self.window + rw), min(n_tok, i + self.window + 1 - rw)
             if not self.cbow:
+                if hi - lo <= 1:  # an empty window trains nothing and is no center (include/w2v_dev.h)
+                    continue
                 x = self.W[c].copy()  # held fixed over the window
                 g = np.zeros_like(x)
                 slot = 0

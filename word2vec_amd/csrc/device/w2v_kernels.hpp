@@ -612,6 +612,11 @@ __device__ __forceinline__ void sg_center(const TrainArgs& a, float* lds, const 
                                           uint32_t s, float alpha, const uint32_t*& rp, Counters& cnt, int lane) {
   const int lo = max(0, i - a.window + rw), hi = min(len, i + a.window + 1 - rw);
   const int span = hi - lo;
+  // An empty window (a one-token sentence) trains nothing and is not counted,
+  // as for CBOW. Its W.row(center) += 0 must not run either: on a plain
+  // (Hogwild) row it is a load and a store of the unchanged row, and a store
+  // that lands after another wave's update of that row takes the update back.
+  if (span <= 1) return;
   const bool hot_c = c < a.hot_wc;
   float x[NV], g[NV];
   if (a.strict) drain_vmem();
