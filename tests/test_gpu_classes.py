@@ -25,9 +25,16 @@ def same_bits(a, b):
 
 
 # ---- 1. assign against the reference ---------------------------------------------------------
-@pytest.mark.parametrize("V,d,k,seed", [(1031, 48, 17, 2), (600, 700, 33, 3), (5000, 300, 500, 4), (333, 400, 21, 5)])
+# 4, 7, 8, 13, 16, 19, 20, 24, 32 and 33 blocks of 16 columns: every instantiated resident width, and the
+# streaming kernel
+INSTANCE_WIDTHS = [64, 112, 128, 208, 256, 304, 320, 384, 512, 528]
+
+
+@pytest.mark.parametrize("V,d,k,seed", [(1031, 48, 17, 2), (600, 700, 33, 3), (5000, 300, 500, 4), (333, 400, 21, 5)] +
+                         [(333, d, 21, 5) for d in INSTANCE_WIDTHS])
 def test_assign_matches_reference(V, d, k, seed):
-    """The last shape takes the one-tile-per-wave kernel (rows of 321 to 512 floats)."""
+    """(333, 400, 21, 5) takes the one-tile-per-wave kernel (rows of 321 to 512 floats); the shapes after it
+    take every instantiated width in turn."""
     rows, cen = K.random_rows(V, d, seed), K.random_centroids(k, d, seed + 10)
     share = (K.top_two_gap(K.cosines(rows, cen)) > 2 * tol(d)).mean()
     assert share >= 0.97  # on the reference alone

@@ -88,6 +88,29 @@ def test_vectors_tail_tile_partial_block_max_k():
         assert np.array_equal(ids, ids2) and np.array_equal(sc.view(np.uint32), sc2.view(np.uint32))
 
 
+# 4, 7, 8, 13, 16, 19, 20, 24, 32 and 33 blocks of 16 columns: every instantiated resident width, and the
+# streaming kernel
+INSTANCE_WIDTHS = [64, 112, 128, 208, 256, 304, 320, 384, 512, 528]
+
+
+@pytest.mark.parametrize("d", INSTANCE_WIDTHS)
+def test_every_instantiated_width(d):
+    """V 333 (a tail tile), nq 40 (a partial query block), k 5, random non-unit query vectors, at each width."""
+    V, nq, k = 333, 40, 5
+    rows = make_rows(V, d, 2)
+    rng = np.random.default_rng(12)
+    q = (rng.standard_normal((nq, d)) * rng.uniform(0.01, 30.0, size=(nq, 1))).astype(np.float32)
+    cos = R.cosines(rows, q)
+    with NearestIndex.from_matrix(rows) as index:
+        ids, sc = index.query_vectors(q, k=k)
+        # on the reference alone 0.85 (d 528) to 1.00 of the queries have clear gaps
+        assert_matches_reference(cos, ids, sc, k, d, min_clear=0.80)
+        assert index.plan()["query_block"] == (128 if d <= 320 else 64)
+        index.set_strip_rows(16)  # 21 strips, the last one 13 rows
+        ids2, sc2 = index.query_vectors(q, k=k)
+        assert np.array_equal(ids, ids2) and np.array_equal(sc.view(np.uint32), sc2.view(np.uint32))
+
+
 def test_wide_rows_padding_and_long_k_loop():
     """V 3000, d 700 (padded to 704: the kernel without resident query fragments), nq 64, k 10."""
     V, d, nq, k = 3000, 700, 64, 10

@@ -279,13 +279,6 @@ int init_device(w2v_dev* h) {
   return W2V_OK;
 }
 
-// At least n elements (the contents are not kept).
-template <class T>
-int score_grow(w2v::DevBuf<T>& b, int64_t n) {
-  const size_t need = (size_t)(n > 0 ? n : 1);
-  return b.size() >= need ? W2V_OK : b.alloc(need);
-}
-
 }  // namespace
 
 extern "C" {
@@ -1334,13 +1327,16 @@ int w2v_dev_score(w2v_dev* h, const int32_t* ids, int64_t n_tok, const int64_t* 
   for (int64_t s = 0; s < n_sent; ++s) item_off[(size_t)s + 1] = item_off[(size_t)s] + (soff[s + 1] - soff[s] + item - 1) / item;
   const int64_t n_items = item_off[(size_t)n_sent];
   int rc;
-  if ((rc = score_grow(h->score_item_off, n_sent + 1)) || (rc = score_grow(h->score_part_ll, n_items)) ||
-      (rc = score_grow(h->score_part_targets, n_items)) || (rc = score_grow(h->score_part_nonfinite, n_items)) ||
-      (rc = score_grow(h->score_ll, n_sent)) || (rc = score_grow(h->score_targets, n_sent)) ||
-      (rc = score_grow(h->score_ctr, w2v::kScoreCounters)))
+  // no empty buffers: nothing to score still gets one element each
+  const size_t items1 = (size_t)std::max<int64_t>(n_items, 1), sents1 = (size_t)std::max<int64_t>(n_sent, 1),
+               toks1 = (size_t)std::max<int64_t>(n_tok, 1);
+  if ((rc = h->score_item_off.reserve((size_t)n_sent + 1)) || (rc = h->score_part_ll.reserve(items1)) ||
+      (rc = h->score_part_targets.reserve(items1)) || (rc = h->score_part_nonfinite.reserve(items1)) ||
+      (rc = h->score_ll.reserve(sents1)) || (rc = h->score_targets.reserve(sents1)) ||
+      (rc = h->score_ctr.reserve((size_t)w2v::kScoreCounters)))
     return rc;
   if (!resident) {
-    if ((rc = score_grow(h->score_ids, n_tok)) || (rc = score_grow(h->score_soff, n_sent + 1))) return rc;
+    if ((rc = h->score_ids.reserve(toks1)) || (rc = h->score_soff.reserve((size_t)n_sent + 1))) return rc;
     if (n_tok > 0) W2V_HIP_TRY(hipMemcpy(h->score_ids.get(), ids, n_tok * sizeof(int32_t), hipMemcpyHostToDevice));
     W2V_HIP_TRY(hipMemcpy(h->score_soff.get(), soff, (n_sent + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
   }

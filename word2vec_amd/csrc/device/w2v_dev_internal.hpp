@@ -59,6 +59,9 @@ class DevBuf {
     p_ = p, n_ = n;
     return W2V_OK;
   }
+  // At least n elements: scratch that only grows. The contents are not kept;
+  // a failure leaves the buffer as it was.
+  int reserve(size_t n) { return n <= n_ ? W2V_OK : alloc(n); }
 
  private:
   T* p_ = nullptr;

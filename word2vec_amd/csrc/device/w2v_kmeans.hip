@@ -27,8 +27,8 @@
 //                     own pitch, and walks the unit centroids 16 at a time in
 //                     the B fragment layout (the next tile's loads in flight
 //                     behind this tile's MFMAs). Products are
-//                     v_mfma_f32_16x16x4_f32 in nn_score_kernel's order (blocks
-//                     ascending, two accumulators added at the end). The running
+//                     v_mfma_f32_16x16x4_f32 in the one order w2v_tiles.hpp
+//                     states. The running
 //                     best (score, class) of a row lives in registers: `>`
 //                     rejects NaN and the invalid / tail centroids are masked,
 //                     +inf is rejected beside it, and centroids arrive in
@@ -53,16 +53,14 @@
 
 #include "w2v_dev.h"
 #include "w2v_dev_internal.hpp"
-#include "w2v_mfma.hpp"
 #include "w2v_nn_internal.hpp"
+#include "w2v_tiles.hpp"
 #include "w2v_wave.hpp"
 
 namespace w2v {
 
 constexpr int kKmMaxClasses = 65536;
 constexpr int kKmMaxIterations = 1000;
-constexpr int kKmWaves = 4;          // wavefronts per workgroup
-constexpr int kKmMaxDim = 2048;      // w2v_nn's widest row
 constexpr int kKmScan = 1024;        // update: rows of the class array a wave scans per step
 constexpr int kKmQueue = 128;        // update: a wave's member queue (flushed from 64 on)
 constexpr int kKmBatch = 8;          // update: member rows in flight per wave
@@ -72,15 +70,15 @@ constexpr int kKmGridTarget = 256;   // update: cut rows into column slabs while
 __global__ __launch_bounds__(256) void km_init_kernel(const float* rows, int64_t n_rows, int64_t pitch, int cols,
                                                       const int32_t* in, int n_classes, int32_t* out) {
   const int lane = lane_id();
-  const int64_t r = (int64_t)blockIdx.x * kKmWaves + (threadIdx.x >> 6);
+  const int64_t r = (int64_t)blockIdx.x * kDenseWaves + (threadIdx.x >> 6);
   if (r >= n_rows) return;  // wave-uniform
   const float* p = rows + r * pitch;
   bool fin = true;
-  for (int c = 4 * lane; c < cols; c += 4 * kWave) {
+  row_walk(lane, cols, [&](int c) {
     const f32x4 v = *reinterpret_cast<const f32x4*>(p + c);
     fin = fin && __builtin_isfinite(v[0]) && __builtin_isfinite(v[1]) && __builtin_isfinite(v[2]) &&
           __builtin_isfinite(v[3]);
-  }
+  });
   const bool ok = ballot(!fin) == 0ull;
   if (lane == 0) out[r] = ok ? (in ? in[r] : (int32_t)(r % n_classes)) : -1;
 }
@@ -90,15 +88,14 @@ __global__ __launch_bounds__(256) void km_init_kernel(const float* rows, int64_t
 __global__ __launch_bounds__(256) void km_unit_kernel(const float* in, float* out, int n, int n16, int cols,
                                                       int32_t* valid) {
   const int lane = lane_id();
-  const int g = (int)(blockIdx.x * kKmWaves + (threadIdx.x >> 6));
+  const int g = (int)(blockIdx.x * kDenseWaves + (threadIdx.x >> 6));
   if (g >= n16) return;  // wave-uniform
-  constexpr int kVec = kKmMaxDim / (4 * kWave);
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-  f32x4 acc[kVec];
+  f32x4 acc[kRowVecs];
   bool fin = true, nz = false;
   float s = 0.f;
 #pragma unroll
-  for (int v = 0; v < kVec; ++v) {
+  for (int v = 0; v < kRowVecs; ++v) {
     const int c = 4 * lane + 4 * kWave * v;
     acc[v] = (g < n && c < cols) ? *reinterpret_cast<const f32x4*>(in + (int64_t)g * cols + c) : zero;
 #pragma unroll
@@ -106,12 +103,12 @@ __global__ __launch_bounds__(256) void km_unit_kernel(const float* in, float* ou
       fin = fin && __builtin_isfinite(acc[v][e]);
       nz = nz || acc[v][e] != 0.f;
     }
-    s += acc[v][0] * acc[v][0] + acc[v][1] * acc[v][1] + acc[v][2] * acc[v][2] + acc[v][3] * acc[v][3];
+    s += sum_sq(acc[v]);
   }
   s = wave_sum(s);
-  const float sc = 1.0f / fmaxf(sqrtf(s), 1e-12f);
+  const float sc = unit_scale(s);
 #pragma unroll
-  for (int v = 0; v < kVec; ++v) {
+  for (int v = 0; v < kRowVecs; ++v) {
     const int c = 4 * lane + 4 * kWave * v;
     if (c < cols) *reinterpret_cast<f32x4*>(out + (int64_t)g * cols + c) = acc[v] * sc;
   }
@@ -131,13 +128,13 @@ struct KmUpdateArgs {
 };
 
 __global__ __launch_bounds__(256) void km_update_kernel(KmUpdateArgs a) {
-  extern __shared__ float km_lds[];  // [kKmWaves][slab_cols] partial sums, then [kKmWaves][kKmQueue] member rows
+  extern __shared__ float km_lds[];  // [kDenseWaves][slab_cols] partial sums, then [kDenseWaves][kKmQueue] member rows
   const int lane = lane_id();
   const int wave = (int)(threadIdx.x >> 6);
   const int c = (int)(blockIdx.x / (unsigned)a.nslab);
   const int slab = (int)(blockIdx.x % (unsigned)a.nslab);
   const int c0 = slab * a.slab_cols, c1 = min(a.cols, c0 + a.slab_cols);
-  int* const queue = reinterpret_cast<int*>(km_lds + kKmWaves * a.slab_cols) + wave * kKmQueue;
+  int* const queue = reinterpret_cast<int*>(km_lds + kDenseWaves * a.slab_cols) + wave * kKmQueue;
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
   const int cl0 = c0 + 4 * lane, cl1 = cl0 + 4 * kWave;
   const bool on0 = cl0 < c1, on1 = cl1 < c1;
@@ -176,13 +173,13 @@ __global__ __launch_bounds__(256) void km_update_kernel(KmUpdateArgs a) {
     for (int j = 0; j < kVecs; ++j)
       nxt[j] = *reinterpret_cast<const int4*>(a.cls + (int64_t)wave * kKmScan + 4 * kWave * j + 4 * lane);
   }
-  for (int64_t ch = wave; ch < nchunk; ch += kKmWaves) {
+  for (int64_t ch = wave; ch < nchunk; ch += kDenseWaves) {
 #pragma unroll
     for (int j = 0; j < kVecs; ++j) cur[j] = nxt[j];
-    if (ch + kKmWaves < nchunk) {
+    if (ch + kDenseWaves < nchunk) {
 #pragma unroll
       for (int j = 0; j < kVecs; ++j)
-        nxt[j] = *reinterpret_cast<const int4*>(a.cls + (ch + kKmWaves) * kKmScan + 4 * kWave * j + 4 * lane);
+        nxt[j] = *reinterpret_cast<const int4*>(a.cls + (ch + kDenseWaves) * kKmScan + 4 * kWave * j + 4 * lane);
     }
 #pragma unroll
     for (int j = 0; j < kVecs; ++j) {
@@ -207,7 +204,7 @@ __global__ __launch_bounds__(256) void km_update_kernel(KmUpdateArgs a) {
   for (int k = (int)threadIdx.x; k < c1 - c0; k += (int)blockDim.x) {
     float s = km_lds[k];
 #pragma unroll
-    for (int w = 1; w < kKmWaves; ++w) s += km_lds[w * a.slab_cols + k];
+    for (int w = 1; w < kDenseWaves; ++w) s += km_lds[w * a.slab_cols + k];
     a.sums[(int64_t)c * a.cols + c0 + k] = s;
   }
 }
@@ -233,9 +230,8 @@ struct KmAssignArgs {
   unsigned long long* moved;
 };
 
-// NB > 0: the fragments of rows up to 16 NB floats stay in registers; NB == 0:
-// any width, the fragments are re-read per centroid tile. QT: 16-row tiles per
-// wave (every centroid fragment a wave loads feeds QT MFMAs).
+// NB, QT and the order of the tile product: w2v_tiles.hpp. A: the row tiles, B:
+// the centroid tiles. nn_score_kernel (w2v_nn.hip) has the same loop.
 template <int NB, int QT>
 __global__ __launch_bounds__(256) void km_assign_kernel(KmAssignArgs a) {
   constexpr int NR = NB > 0 ? NB : 1;
@@ -243,7 +239,7 @@ __global__ __launch_bounds__(256) void km_assign_kernel(KmAssignArgs a) {
   const int lane = lane_id();
   const int wave = (int)(threadIdx.x >> 6);
   const int q4 = lane >> 4, col = lane & 15;
-  const int64_t r0 = ((int64_t)blockIdx.x * kKmWaves + wave) * NQ;
+  const int64_t r0 = ((int64_t)blockIdx.x * kDenseWaves + wave) * NQ;
   if (r0 >= a.n_rows) return;  // wave-uniform; the kernel has no barrier
   const int nkb = a.cols >> 4;
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
@@ -401,7 +397,7 @@ int init_state(w2v_nn* x, KmState& st, int32_t k) {
 
 // out[r] = in[r] (null: r mod k) for finite rows, -1 for the others.
 int launch_init(w2v_nn* x, const int32_t* in, int32_t k, int32_t* out) {
-  const unsigned grid = (unsigned)((x->n_rows + w2v::kKmWaves - 1) / w2v::kKmWaves);
+  const unsigned grid = (unsigned)((x->n_rows + w2v::kDenseWaves - 1) / w2v::kDenseWaves);
   hipLaunchKernelGGL(w2v::km_init_kernel, dim3(grid), dim3(256), 0, x->stream, x->rows, x->n_rows, x->pitch, x->cols, in,
                      k, out);
   W2V_HIP_TRY(hipGetLastError());
@@ -409,7 +405,7 @@ int launch_init(w2v_nn* x, const int32_t* in, int32_t k, int32_t* out) {
 }
 
 int launch_unit(w2v_nn* x, KmState& st, const float* in, float* out) {
-  const unsigned grid = (unsigned)((st.k16 + w2v::kKmWaves - 1) / w2v::kKmWaves);
+  const unsigned grid = (unsigned)((st.k16 + w2v::kDenseWaves - 1) / w2v::kDenseWaves);
   hipLaunchKernelGGL(w2v::km_unit_kernel, dim3(grid), dim3(256), 0, x->stream, in, out, st.k, st.k16, x->cols,
                      st.valid.get());
   W2V_HIP_TRY(hipGetLastError());
@@ -431,27 +427,15 @@ int step_centroids(w2v_nn* x, KmState& st, const int32_t* cls) {
   a.slab_cols = (int32_t)round_up((x->cols + slabs - 1) / slabs, 16);
   a.nslab = (x->cols + a.slab_cols - 1) / a.slab_cols;
   a.sums = st.sums.get();
-  const size_t lds = ((size_t)w2v::kKmWaves * a.slab_cols + (size_t)w2v::kKmWaves * w2v::kKmQueue) * sizeof(float);
+  const size_t lds = ((size_t)w2v::kDenseWaves * a.slab_cols + (size_t)w2v::kDenseWaves * w2v::kKmQueue) * sizeof(float);
   hipLaunchKernelGGL(w2v::km_update_kernel, dim3((unsigned)(st.k * a.nslab)), dim3(256), lds, x->stream, a);
   W2V_HIP_TRY(hipGetLastError());
   return launch_unit(x, st, st.sums.get(), st.raw.get());
 }
 
 using AssignFn = void (*)(w2v::KmAssignArgs);
-// nn_score_kernel's instantiated block counts (w2v_nn.hip, score_kernel_for).
-AssignFn assign_kernel_for(int cols, int* rows_per_block) {
-  const int nkb = cols / 16;
-#define W2V_KM_PICK(NB, QT)                                   \
-  if (nkb <= NB) {                                            \
-    *rows_per_block = w2v::kKmWaves * w2v::kSnTile * QT;      \
-    return w2v::km_assign_kernel<NB, QT>;                     \
-  }
-  W2V_KM_PICK(4, 2) W2V_KM_PICK(7, 2) W2V_KM_PICK(8, 2) W2V_KM_PICK(13, 2) W2V_KM_PICK(16, 2) W2V_KM_PICK(19, 2)
-  W2V_KM_PICK(20, 2) W2V_KM_PICK(24, 1) W2V_KM_PICK(32, 1)
-#undef W2V_KM_PICK
-  *rows_per_block = w2v::kKmWaves * w2v::kSnTile;
-  return w2v::km_assign_kernel<0, 1>;
-}
+// The instance for rows of `cols` floats (w2v_tiles.hpp) and the rows its workgroup owns.
+AssignFn assign_kernel_for(int cols, int* rows_per_block) { W2V_TILE_KERNEL_FOR(w2v::km_assign_kernel, cols, rows_per_block); }
 
 // The assign step against st.raw (any length): st.unit <- its unit centroids,
 // out / st.score <- each row's class and score, st.moved <- rows with out != prev.

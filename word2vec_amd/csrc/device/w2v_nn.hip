@@ -34,9 +34,7 @@
 //
 // Order: score descending, then row id ascending, everywhere, so the answer
 // does not depend on the strip count or on arrival order. A row's score has
-// one accumulation order (blocks ascending; of a block's four products the
-// first and third go into one accumulator, the second and fourth into
-// another, and the two are added at the end): it does not depend on the
+// one accumulation order (stated in w2v_tiles.hpp): it does not depend on the
 // tile slot, the strip or the launch, so duplicate rows tie bit-exactly and a
 // call repeats bit-identically. A non-finite score fails the threshold
 // compare (NaN and -inf fail `>`; +inf is rejected beside it); rows past the
@@ -59,16 +57,14 @@
 
 #include "w2v_dev.h"
 #include "w2v_dev_internal.hpp"
-#include "w2v_mfma.hpp"
 #include "w2v_nn_internal.hpp"
+#include "w2v_tiles.hpp"
 #include "w2v_wave.hpp"
 
 namespace w2v {
 
-constexpr int kNnMaxDim = 2048;
 constexpr int kNnMaxK = 64;
 constexpr int kNnMaxTerms = 8;
-constexpr int kNnWaves = 4;                       // wavefronts per workgroup
 constexpr int kNnExclRegs = 8;                    // excluded ids per query kept in registers
 constexpr int64_t kNnStripBytes = 16 << 20;       // auto strip: rows of this many bytes at most ...
 constexpr int64_t kNnStripMinRows = 256;          //   ... and this many rows at least ...
@@ -79,16 +75,13 @@ constexpr int64_t kNnChunkQueries = 32768;        // queries per chunk at most
 __global__ __launch_bounds__(256) void nn_norm_kernel(const float* rows, int64_t n_rows, int64_t pitch, int cols,
                                                       float* inv_norm) {
   const int lane = lane_id();
-  const int64_t r = (int64_t)blockIdx.x * kNnWaves + (threadIdx.x >> 6);
+  const int64_t r = (int64_t)blockIdx.x * kDenseWaves + (threadIdx.x >> 6);
   if (r >= n_rows) return;  // wave-uniform
   const float* p = rows + r * pitch;
   float s = 0.f;
-  for (int c = 4 * lane; c < cols; c += 4 * kWave) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(p + c);
-    s += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
-  }
+  row_walk(lane, cols, [&](int c) { s += sum_sq(*reinterpret_cast<const f32x4*>(p + c)); });
   s = wave_sum(s);
-  if (lane == 0) inv_norm[r] = 1.0f / fmaxf(sqrtf(s), 1e-12f);
+  if (lane == 0) inv_norm[r] = unit_scale(s);
 }
 
 // q[gq] (cols floats, in place for the vector form) <- the unit-length query.
@@ -96,14 +89,13 @@ __global__ __launch_bounds__(256) void nn_query_kernel(const float* rows, int64_
                                                        const int32_t* ids, const float* weights, int terms, float* q,
                                                        int64_t nq, int cols) {
   const int lane = lane_id();
-  const int64_t gq = (int64_t)blockIdx.x * kNnWaves + (threadIdx.x >> 6);
+  const int64_t gq = (int64_t)blockIdx.x * kDenseWaves + (threadIdx.x >> 6);
   if (gq >= nq) return;  // wave-uniform
-  constexpr int kVec = kNnMaxDim / (4 * kWave);  // 16-B vectors per lane covering the widest row
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-  f32x4 acc[kVec];
+  f32x4 acc[kRowVecs];
   float* out = q + gq * cols;
 #pragma unroll
-  for (int v = 0; v < kVec; ++v) {
+  for (int v = 0; v < kRowVecs; ++v) {
     const int c = 4 * lane + 4 * kWave * v;
     acc[v] = (ids == nullptr && c < cols) ? *reinterpret_cast<const f32x4*>(out + c) : zero;
   }
@@ -114,7 +106,7 @@ __global__ __launch_bounds__(256) void nn_query_kernel(const float* rows, int64_
       const float w = weights[gq * terms + t] * inv_norm[id];
       const float* p = rows + (int64_t)id * pitch;
 #pragma unroll
-      for (int v = 0; v < kVec; ++v) {
+      for (int v = 0; v < kRowVecs; ++v) {
         const int c = 4 * lane + 4 * kWave * v;
         if (c < cols) acc[v] += w * *reinterpret_cast<const f32x4*>(p + c);
       }
@@ -122,11 +114,11 @@ __global__ __launch_bounds__(256) void nn_query_kernel(const float* rows, int64_
   }
   float s = 0.f;
 #pragma unroll
-  for (int v = 0; v < kVec; ++v) s += acc[v][0] * acc[v][0] + acc[v][1] * acc[v][1] + acc[v][2] * acc[v][2] + acc[v][3] * acc[v][3];
+  for (int v = 0; v < kRowVecs; ++v) s += sum_sq(acc[v]);
   s = wave_sum(s);
-  const float sc = 1.0f / fmaxf(sqrtf(s), 1e-12f);
+  const float sc = unit_scale(s);
 #pragma unroll
-  for (int v = 0; v < kVec; ++v) {
+  for (int v = 0; v < kRowVecs; ++v) {
     const int c = 4 * lane + 4 * kWave * v;
     if (c < cols) *reinterpret_cast<f32x4*>(out + c) = acc[v] * sc;
   }
@@ -176,12 +168,8 @@ __device__ __forceinline__ float nn_insert(float* ls, int* li, int k, int lane, 
   return pos == k - 1 ? s : readlane_f(es, k - 2);
 }
 
-// NB > 0: the query fragments of rows up to 16 NB floats stay in registers;
-// NB == 0: any width, the fragments are re-read (L1 / L2) per candidate tile.
-// QT: 16-query tiles per wave. Every candidate fragment a wave loads feeds QT
-// MFMAs, so QT = 2 halves the L1 / L2 traffic per FLOP and gives the MFMA
-// pipe four independent accumulators (a dependent v_mfma_f32_16x16x4_f32
-// issues every 40 cycles, an independent one every 32).
+// NB, QT and the order of the tile product: w2v_tiles.hpp. A: the query tiles,
+// B: the candidate tiles. km_assign_kernel (w2v_kmeans.hip) has the same loop.
 template <int NB, int QT>
 __global__ __launch_bounds__(256) void nn_score_kernel(NnArgs a) {
   extern __shared__ float nn_lds[];
@@ -192,7 +180,7 @@ __global__ __launch_bounds__(256) void nn_score_kernel(NnArgs a) {
   const int q4 = lane >> 4, col = lane & 15;
   const int64_t strip = blockIdx.x / (unsigned)a.nqb;
   const int qb = (int)(blockIdx.x % (unsigned)a.nqb);
-  const int64_t q0 = ((int64_t)qb * kNnWaves + wave) * NQ;
+  const int64_t q0 = ((int64_t)qb * kDenseWaves + wave) * NQ;
   if (q0 >= a.nq) return;  // wave-uniform; the kernel has no barrier
   const int k = a.k;
   float* const ls = nn_lds + wave * (2 * NQ * k);
@@ -348,7 +336,7 @@ __global__ __launch_bounds__(256) void nn_score_kernel(NnArgs a) {
 __global__ __launch_bounds__(256) void nn_merge_kernel(const float* p_score, const int32_t* p_id, int64_t n, int k,
                                                        int64_t nq, float* o_score, int32_t* o_id) {
   const int lane = lane_id();
-  const int64_t gq = (int64_t)blockIdx.x * kNnWaves + (threadIdx.x >> 6);
+  const int64_t gq = (int64_t)blockIdx.x * kDenseWaves + (threadIdx.x >> 6);
   if (gq >= nq) return;  // wave-uniform
   const float* ps = p_score + gq * n;
   const int32_t* pi = p_id + gq * n;
@@ -398,13 +386,8 @@ __global__ __launch_bounds__(256) void nn_merge_kernel(const float* p_score, con
 
 namespace {
 
-template <class T>
-int grow(w2v::DevBuf<T>& b, size_t need) {
-  return need <= b.size() ? W2V_OK : b.alloc(need);
-}
-
 int compute_norms(w2v_nn* x) {
-  const unsigned grid = (unsigned)((x->n_rows + w2v::kNnWaves - 1) / w2v::kNnWaves);
+  const unsigned grid = (unsigned)((x->n_rows + w2v::kDenseWaves - 1) / w2v::kDenseWaves);
   hipLaunchKernelGGL(w2v::nn_norm_kernel, dim3(grid), dim3(256), 0, x->stream, x->rows, x->n_rows, x->pitch, x->cols,
                      x->inv_norm.get());
   W2V_HIP_TRY(hipGetLastError());
@@ -413,24 +396,8 @@ int compute_norms(w2v_nn* x) {
 }
 
 using ScoreFn = void (*)(w2v::NnArgs);
-// The kernel whose resident block count is the smallest instantiated one that
-// covers the row (the usual dims exactly: 64, 100, 128, 200, 256, 300, 320
-// floats), with two query tiles per wave while their fragments fit the
-// register file beside two candidate tiles (rows up to 320 floats) and one
-// beyond; past 512 floats the kernel that re-reads the fragments.
-ScoreFn score_kernel_for(int cols, int* query_block) {
-  const int nkb = cols / 16;
-#define W2V_NN_PICK(NB, QT)                                   \
-  if (nkb <= NB) {                                            \
-    *query_block = w2v::kNnWaves * w2v::kSnTile * QT;         \
-    return w2v::nn_score_kernel<NB, QT>;                      \
-  }
-  W2V_NN_PICK(4, 2) W2V_NN_PICK(7, 2) W2V_NN_PICK(8, 2) W2V_NN_PICK(13, 2) W2V_NN_PICK(16, 2) W2V_NN_PICK(19, 2)
-  W2V_NN_PICK(20, 2) W2V_NN_PICK(24, 1) W2V_NN_PICK(32, 1)
-#undef W2V_NN_PICK
-  *query_block = w2v::kNnWaves * w2v::kSnTile;
-  return w2v::nn_score_kernel<0, 1>;
-}
+// The instance for rows of `cols` floats (w2v_tiles.hpp) and the queries its workgroup owns.
+ScoreFn score_kernel_for(int cols, int* query_block) { W2V_TILE_KERNEL_FOR(w2v::nn_score_kernel, cols, query_block); }
 int query_block_for(int cols) {
   int qb = 0;
   (void)score_kernel_for(cols, &qb);
@@ -441,7 +408,7 @@ int query_block_for(int cols) {
 // nullptr) or described by x->ids / x->wts (by-row form), to out[0 .. n k).
 int run_chunk(w2v_nn* x, int64_t n, bool by_row, int32_t terms, const int32_t* excl_d, int32_t n_excl, int64_t limit,
               int32_t k, int64_t strip_rows, int64_t strips, int32_t* out_ids, float* out_scores) {
-  const unsigned qgrid = (unsigned)((n + w2v::kNnWaves - 1) / w2v::kNnWaves);
+  const unsigned qgrid = (unsigned)((n + w2v::kDenseWaves - 1) / w2v::kDenseWaves);
   hipLaunchKernelGGL(w2v::nn_query_kernel, dim3(qgrid), dim3(256), 0, x->stream, x->rows, x->pitch,
                      x->inv_norm.get(), by_row ? x->ids.get() : (const int32_t*)nullptr, x->wts.get(), terms,
                      x->q.get(), n, x->cols);
@@ -510,14 +477,14 @@ int run_query(w2v_nn* x, const float* q, const int32_t* ids, const float* weight
   chunk = std::min(chunk, (nq + qblock - 1) / qblock * qblock);
   int rc;
   const size_t q_n = (size_t)chunk * x->cols, q_bytes = q_n * sizeof(float);
-  if ((rc = grow(x->q, q_n))) return rc;
-  if ((rc = grow(x->p_score, (size_t)chunk * strips * k))) return rc;
-  if ((rc = grow(x->p_id, (size_t)chunk * strips * k))) return rc;
-  if ((rc = grow(x->o_score, (size_t)chunk * k))) return rc;
-  if ((rc = grow(x->o_id, (size_t)chunk * k))) return rc;
+  if ((rc = x->q.reserve(q_n))) return rc;
+  if ((rc = x->p_score.reserve((size_t)chunk * strips * k))) return rc;
+  if ((rc = x->p_id.reserve((size_t)chunk * strips * k))) return rc;
+  if ((rc = x->o_score.reserve((size_t)chunk * k))) return rc;
+  if ((rc = x->o_id.reserve((size_t)chunk * k))) return rc;
   const int32_t n_ids = q ? n_excl : terms;  // ids per query in x->ids: the exclusions, or the terms
-  if (n_ids > 0 && (rc = grow(x->ids, (size_t)chunk * n_ids))) return rc;
-  if (!q && (rc = grow(x->wts, (size_t)chunk * terms))) return rc;
+  if (n_ids > 0 && (rc = x->ids.reserve((size_t)chunk * n_ids))) return rc;
+  if (!q && (rc = x->wts.reserve((size_t)chunk * terms))) return rc;
   for (int64_t c0 = 0; c0 < nq; c0 += chunk) {
     const int64_t n = std::min(chunk, nq - c0);
     W2V_HIP_TRY(hipMemsetAsync(x->q.get(), 0, q_bytes, x->stream));  // padding columns and tail queries are zero
@@ -556,7 +523,7 @@ int check_common(const char* fn, w2v_nn* x, int64_t nq, int64_t restrict_rows, i
 extern "C" {
 
 int w2v_nn_limits(int32_t* max_dim, int32_t* max_k, int32_t* max_terms) {
-  if (max_dim) *max_dim = w2v::kNnMaxDim;
+  if (max_dim) *max_dim = w2v::kDenseMaxDim;
   if (max_k) *max_k = w2v::kNnMaxK;
   if (max_terms) *max_terms = w2v::kNnMaxTerms;
   return W2V_OK;
@@ -566,8 +533,8 @@ int w2v_nn_create(int32_t device, const float* rows, int64_t n_rows, int32_t dim
   if (!out) return w2v::set_error(W2V_ERR_ARG, "w2v_nn_create: null output");
   *out = nullptr;
   if (!rows) return w2v::set_error(W2V_ERR_ARG, "w2v_nn_create: null matrix");
-  if (dim < 1 || dim > w2v::kNnMaxDim)
-    return w2v::set_error(W2V_ERR_ARG, "w2v_nn_create: dim must be in [1, " + std::to_string(w2v::kNnMaxDim) + "], got " + std::to_string(dim));
+  if (dim < 1 || dim > w2v::kDenseMaxDim)
+    return w2v::set_error(W2V_ERR_ARG, "w2v_nn_create: dim must be in [1, " + std::to_string(w2v::kDenseMaxDim) + "], got " + std::to_string(dim));
   if (n_rows < 1 || n_rows > (int64_t)0x7fffffff)
     return w2v::set_error(W2V_ERR_ARG, "w2v_nn_create: n_rows must be in [1, 2^31), got " + std::to_string(n_rows));
   w2v::Range range_("w2v_nn_create");
